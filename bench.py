@@ -4,11 +4,14 @@
 One "step" = one pass of the hot path over one batch of synthetic input per GPU:
   pixel_values [B*1024, 1176] bf16 (B images of 448x448, resident in HBM)
     -> Qwen2-VL vision tower -> prompt prefill (S = 286) -> 16 greedy decode steps -> token ids on host.
-Reported `value` = images/s over all ranks (weak scaling: per-GPU batch fixed).  The same JSON line carries
-the label-cosine/s of the scorer leg, the MFMA roofline of the dominant kernel (bf16 GEMM, HIP events
-around every launch of the timed region) and the reference's CPU HuggingFace path timed on the host cores.
+Reported `value` = images/s over all ranks (weak scaling: per-GPU batch fixed), `ms_per_step` = one timed step; the
+line also carries the MFMA roofline of the dominant kernel (bf16 GEMM, HIP events around every launch of the timed
+region).  With --full the same JSON line also carries the label-cosine/s of the scorer leg, the other legs and checks,
+and the reference's CPU HuggingFace path timed on the host cores.  --dump-outputs DIR writes the last timed step's
+token ids (DIR/tokens.npy).
 
   python bench.py --gpus 1 --steps 3 --warmup 1
+  python bench.py --gpus 1 --steps 3 --warmup 1 --full
   python bench.py --gpus 8 --steps 3 --warmup 1          # spawns its own 8 ranks (one process per GPU, RCCL)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 \
          bench.py --gpus 8 --steps 3 --warmup 1          # or under a launcher that already set RANK / WORLD_SIZE
@@ -859,7 +862,15 @@ def main() -> None:
     ap.add_argument("--dry-run", action="store_true", help="launcher + rendezvous check on CPU (gloo); stops before HIP init")
     ap.add_argument("--one-gpu-value", type=float, default=None,
                     help="images/s of the 1-GPU run: adds scaling_efficiency = value / (N * this) to the line")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: box calibration, batch-invariance check, EOS / image-size / "
+                         "host-input / PIL / decode-regime / label-cosine / other-config legs, CPU baseline + full-size parity gate, "
+                         "big-model legs (without it: set-up, warm-up, the timed steps and the result line only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (token ids) as float32 DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(self_launch(args.gpus))   # nothing above this line has touched the GPU
@@ -1000,7 +1011,7 @@ def main() -> None:
         step()
     sync()
     calib = None
-    if not args.no_calibration and args.model == "7b":   # (the yardstick is a 7B shape; every rank runs it: the ranks stay in step)
+    if args.full and not args.no_calibration and args.model == "7b":   # (the yardstick is a 7B shape; every rank runs it: the ranks stay in step)
         try:
             calib = BoxCalibration(device)
             calib.run()
@@ -1042,6 +1053,68 @@ def main() -> None:
         per_rank_dt, per_rank_own = gathered.view(world, 2)[:, 0].tolist(), gathered.view(world, 2)[:, 1].tolist()
     dt = max(per_rank_dt)                       # max over ranks
     images_per_s = world * B * args.steps / dt
+    if args.dump_outputs:
+        dump_outputs(Path(args.dump_outputs), "tokens" if rank == 0 else f"tokens_rank{rank}", out.numpy(), world)
+
+    # ---- the headline line: everything in it comes from the warm-up and the timed steps above
+    result = None
+    if rank == 0:
+        f_model = flops_per_image(dims, T)
+        # executed FLOPs: what every utilisation figure below is priced on
+        s_prompt = S_TEXT_BEFORE + S_IMG + S_TEXT_AFTER
+        per_chunk = max(1, min(B, (engine.prefill_chunk_tokens - S_TEXT_BEFORE) // (s_prompt - S_TEXT_BEFORE))) if engine.share_prefix else 1
+        f_img = f_model if args.nominal_forward else f_model - pruned_flops_per_image(dims, per_chunk)
+        g = prof["gemm_fp8" if fp8_run else "gemm_bf16"]
+        gemm_tflops = g["work"] / (g["ms"] * 1e-3) / 1e12 if g["ms"] > 0 else 0.0
+        peak = PEAK_FP8_TFLOPS if fp8_run else PEAK_BF16_TFLOPS
+        traffic = None if fp8_run else load_traffic(args, engine, B)
+        result = {
+            "metric": f"images/sec (whole node) {'Qwen2.5-VL-' + args.model[4:].upper() if args.model.startswith('2.5-') else 'Qwen2-VL-' + args.model.upper()} open-world classify; label-cosine/sec",
+            "value": images_per_s, "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "bf16" if not fp8_run else "fp8-e4m3 decoder projections (per-token / per-channel scales), bf16 elsewhere", "data": "synthetic",
+            # (the driver's record keeps the scalars of `config` and `roofline` and the first 120 characters of a string)
+            "config": {"workload": f"Qwen2-VL-{args.model.upper()}{' (fp8 decoder)' if fp8_run else ''}: {B} synthetic 448x448 images/GPU/step, timed from pixel_values "
+                                   f"RESIDENT IN HBM, S=286, {T} forced greedy tokens; (1024 patches -> 256 image tokens per image, seeded random "
+                                   "weights of the real architecture; images strided across ranks, no data-path collective"
+                                   + ("; the same step fed from host uint8 / PIL images: images_per_s_from_host_uint8 / images_per_s_from_pil below)"
+                                      if args.full else ")"),
+                       "images_per_gpu_per_step": B, "prompt_tokens": 286, "new_tokens": T, "parallelism": f"dp{world}",
+                       "timed_region_starts_from": "pixel_values resident in HBM",
+                       **({"tuning": args.tune} if args.tune else {})},
+            "ms_of_each_step": [round((b - a) * 1e3, 1) for a, b in zip([t0] + step_end[:-1], step_end)],   # rank 0: drift under sustained load shows here
+            "per_rank_images_per_s": [B * args.steps / t for t in per_rank_own],   # each rank's own clock, before the closing barrier
+            "rccl_world_size": dist.get_world_size() if dist is not None else 1,
+            "model_flops_per_image": f_model,      # SURVEY.md section 8(d): the model's nominal forward
+            "executed_flops_per_image": f_img,     # minus the last prefill layer's dead rows (see pruned_flops_per_image)
+            "mfma_frac_end_to_end": images_per_s / world * f_img / (PEAK_BF16_TFLOPS * 1e12),  # always against the bf16 peak
+            "roofline": {"bound": "mfma", "kernel": "gemm_fp8_nt_256_kernel (decoder projections)" if fp8_run else "gemm_bf16_nt_kernel (all epilogues)",
+                         "achieved": gemm_tflops, "peak": peak, "unit": "TFLOP/s", "frac": gemm_tflops / peak,
+                         "traffic": traffic["bytes_per_launch"] if traffic else None, "traffic_source": traffic,
+                         "launches": g["launches"], "kernel_ms_total": g["ms"], "share_of_step_time": g["ms"] * 1e-3 / time_or(dt),
+                         "method": "HIP events around every launch of the timed region on the launch stream; achieved = sum(2MNK) / sum(t)",
+                         # the 12 shapes that hold the most time (the full table: --shape-table FILE); `shapes` = how many there are
+                         "by_shape": [{k: (round(v, 3) if isinstance(v, float) else v) for k, v in r.items() if k != "flop_per_launch"}
+                                      for r in (shape_table or [])[:12]],
+                         "shapes": len(shape_table or []),
+                         "by_shape_covers_ms": sum(r["total_ms"] for r in (shape_table or [])[:12])},
+            "roofline_attention": attention_rooflines(prof, dims, B, T, args.steps, dt),
+        }
+        if args.one_gpu_value:
+            result["scaling_efficiency"] = images_per_s / (world * args.one_gpu_value)
+        if fp8_run:
+            b16 = prof["gemm_bf16"]
+            result["bf16_gemm_in_same_run"] = {"tflops": b16["work"] / (b16["ms"] * 1e-3) / 1e12 if b16["ms"] > 0 else 0.0,
+                                               "kernel_ms_total": b16["ms"], "launches": b16["launches"]}
+    if not args.full:   # a plain run ends here: the rest measures and checks other things (--full)
+        if rank == 0:
+            leg_seconds["total_since_process_start"] = round(time.perf_counter() - T_PROCESS_START, 1)
+            result["leg_seconds"] = leg_seconds
+            print(json.dumps(result), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- outside the timed region: image 0's tokens inside the B-image batch == the same image run alone (batch invariance
     # across the chunked vision / prefill launch groups and the batch-size dependent decode kernels)
@@ -1191,33 +1264,9 @@ def main() -> None:
 
     parity_failure = None
     if rank == 0:
-        f_model = flops_per_image(dims, T)
-        # executed FLOPs: what every utilisation figure below is priced on
-        s_prompt = S_TEXT_BEFORE + S_IMG + S_TEXT_AFTER
-        per_chunk = max(1, min(B, (engine.prefill_chunk_tokens - S_TEXT_BEFORE) // (s_prompt - S_TEXT_BEFORE))) if engine.share_prefix else 1
-        f_img = f_model if args.nominal_forward else f_model - pruned_flops_per_image(dims, per_chunk)
-        g = prof["gemm_fp8" if fp8_run else "gemm_bf16"]
-        gemm_tflops = g["work"] / (g["ms"] * 1e-3) / 1e12 if g["ms"] > 0 else 0.0
-        peak = PEAK_FP8_TFLOPS if fp8_run else PEAK_BF16_TFLOPS
-        traffic = None if fp8_run else load_traffic(args, engine, B)
-        result = {
-            "metric": f"images/sec (whole node) {'Qwen2.5-VL-' + args.model[4:].upper() if args.model.startswith('2.5-') else 'Qwen2-VL-' + args.model.upper()} open-world classify; label-cosine/sec",
-            "value": images_per_s, "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "bf16" if not fp8_run else "fp8-e4m3 decoder projections (per-token / per-channel scales), bf16 elsewhere", "data": "synthetic",
-            # (the driver's record keeps the scalars of `config` and `roofline` and the first 120 characters of a string)
-            "config": {"workload": f"Qwen2-VL-{args.model.upper()}{' (fp8 decoder)' if fp8_run else ''}: {B} synthetic 448x448 images/GPU/step, timed from pixel_values "
-                                   f"RESIDENT IN HBM, S=286, {T} forced greedy tokens; (1024 patches -> 256 image tokens per image, seeded random "
-                                   "weights of the real architecture; images strided across ranks, no data-path collective; the same step fed "
-                                   "from host uint8 / PIL images: images_per_s_from_host_uint8 / images_per_s_from_pil below)",
-                       "images_per_gpu_per_step": B, "prompt_tokens": 286, "new_tokens": T, "parallelism": f"dp{world}",
-                       "timed_region_starts_from": "pixel_values resident in HBM",
-                       "images_per_s_from_host_uint8": pcie_images_per_s,
-                       "images_per_s_from_pil": pil.get("images_per_s") if pil else None,
-                       **({"tuning": args.tune} if args.tune else {})},
-            "ms_of_each_step": [round((b - a) * 1e3, 1) for a, b in zip([t0] + step_end[:-1], step_end)],   # rank 0: drift under sustained load shows here
-            "per_rank_images_per_s": [B * args.steps / t for t in per_rank_own],   # each rank's own clock, before the closing barrier
-            "rccl_world_size": dist.get_world_size() if dist is not None else 1,
+        result["config"].update({"images_per_s_from_host_uint8": pcie_images_per_s,
+                                 "images_per_s_from_pil": pil.get("images_per_s") if pil else None})
+        result.update({
             "batch_invariance_check": "ok: image 0's tokens inside the batch == the same image run alone" if invariant else
                                       "MISMATCH: image 0's tokens differ between the batch and a single-image run",
             "images_per_s_from_host_uint8": pcie_images_per_s,  # PCIe-inclusive (H2D + GPU patchify + step), not `value`
@@ -1226,37 +1275,17 @@ def main() -> None:
             "label_cosine_config": {"labels_per_gpu": n_lab, "tokens_per_label": f"uniform 2..{L} (mean {label_tokens / n_lab:.2f}), padded rows are not computed",
                                     "classes": args.scorer_classes, "top_k": 5,
                                     "encoder": "MiniLM-L6 (BERT 6x384) fp32; linears as 3-piece bf16 splits on the bf16 MFMA (fp32-level error, tests/test_scorer_gpu.py)"},
-            "model_flops_per_image": f_model,      # SURVEY.md section 8(d): the model's nominal forward
-            "executed_flops_per_image": f_img,     # minus the last prefill layer's dead rows (see pruned_flops_per_image)
-            "mfma_frac_end_to_end": images_per_s / world * f_img / (PEAK_BF16_TFLOPS * 1e12),  # always against the bf16 peak
-            "roofline": {"bound": "mfma", "kernel": "gemm_fp8_nt_256_kernel (decoder projections)" if fp8_run else "gemm_bf16_nt_kernel (all epilogues)",
-                         "achieved": gemm_tflops, "peak": peak, "unit": "TFLOP/s", "frac": gemm_tflops / peak,
-                         "traffic": traffic["bytes_per_launch"] if traffic else None, "traffic_source": traffic,
-                         "launches": g["launches"], "kernel_ms_total": g["ms"], "share_of_step_time": g["ms"] * 1e-3 / time_or(dt),
-                         "method": "HIP events around every launch of the timed region on the launch stream; achieved = sum(2MNK) / sum(t)",
-                         # the 12 shapes that hold the most time (the full table: --shape-table FILE); `shapes` = how many there are
-                         "by_shape": [{k: (round(v, 3) if isinstance(v, float) else v) for k, v in r.items() if k != "flop_per_launch"}
-                                      for r in (shape_table or [])[:12]],
-                         "shapes": len(shape_table or []),
-                         "by_shape_covers_ms": sum(r["total_ms"] for r in (shape_table or [])[:12])},
-            "roofline_attention": attention_rooflines(prof, dims, B, T, args.steps, dt),
             "roofline_decode": decode_leg,
             "eos_terminated": eos_leg,
             "config2_qwen2vl_2b": cfg2,
             "label_cosine_10k_classes": cos10k,
             "roofline_label_cosine": scorer_rooflines(sprof, n_lab, args.scorer_classes, 5, args.steps, float(sdt.item())),
-        }
+        })
         if calib is not None and calib.runs:
             cal = calib.report(images_per_s / world)
             result["roofline"]["box_calibration_tflops"] = cal["tflops"]
             result["config"]["box_calibration_tflops"] = cal["tflops"]
             result["config"]["value_per_calibration_tflops"] = cal["value_per_calibration_tflops"]
-        if args.one_gpu_value:
-            result["scaling_efficiency"] = images_per_s / (world * args.one_gpu_value)
-        if fp8_run:
-            b16 = prof["gemm_bf16"]
-            result["bf16_gemm_in_same_run"] = {"tflops": b16["work"] / (b16["ms"] * 1e-3) / 1e12 if b16["ms"] > 0 else 0.0,
-                                               "kernel_ms_total": b16["ms"], "launches": b16["launches"]}
         if world == 1 and not args.no_cpu_baseline:
             try:
                 result["cpu_baseline"] = cpu_baseline_lmm(dims, device, 1234, T, pix, out, args.cpu_images, engine, args.cpu_budget_s)
@@ -1553,6 +1582,23 @@ def scorer_rooflines(sprof: dict, n_lab: int, n_cls: int, k: int, steps: int, sd
 
 def time_or(x: float) -> float:
     return x if x > 0 else 1.0
+
+
+DUMP_BYTES = 64 << 20   # --dump-outputs writes at most this much over all ranks
+
+
+def dump_outputs(dirpath: Path, name: str, arr: np.ndarray, world: int) -> None:
+    """`arr` as float32 DIR/<name>.npy (token ids < 2^24 are exact).  Above this rank's share of DUMP_BYTES, a fixed seeded sample of
+    its rows (in order; their indices in DIR/<name>_rows.npy), so that two builds still compare output for output."""
+    a = np.asarray(arr, dtype=np.float32)
+    dirpath.mkdir(parents=True, exist_ok=True)
+    budget = DUMP_BYTES // world
+    if a.nbytes > budget:
+        keep = max(1, budget // (a[0].nbytes + 8))
+        rows = np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))
+        np.save(dirpath / f"{name}_rows.npy", rows.astype(np.float64))
+        a = a[rows]
+    np.save(dirpath / f"{name}.npy", a)
 
 
 if __name__ == "__main__":

@@ -21,7 +21,7 @@ def test_two_ranks_share_one_gpu(gpu):
     env = dict(os.environ, OWC_BENCH_SHARE_GPU="1", MASTER_ADDR="127.0.0.1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--model", "2b", "--batch", "64", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--model", "2b", "--batch", "64", "--steps", "2", "--warmup", "1", "--full",
            "--scorer-labels", "4096", "--no-cpu-baseline", "--no-pil-leg", "--cap-images", "12", "--ragged-images", "256"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=str(ROOT))
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
@@ -73,3 +73,34 @@ def test_two_ranks_share_one_gpu(gpu):
     ls = out["leg_seconds"]
     assert {"setup_weights_inputs", "warmup_and_timed_steps", "eos_terminated", "real_image_sizes", "max_pixels_images", "roofline_decode"} <= set(ls)
     assert abs(sum(v for k, v in ls.items() if k != "total_since_process_start") - ls["total_since_process_start"]) < 2.0
+
+
+def test_plain_run_and_dump_outputs(gpu, tmp_path):
+    """A run without --full: set-up, warm-up, the timed steps and the headline line - none of the other legs - and
+    --dump-outputs writes the last timed step's token ids; a second process with the same inputs returns the same ids."""
+    def run(steps, warmup, out):
+        cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--model", "2b", "--batch", "64", "--steps", str(steps),
+               "--warmup", str(warmup), "--dump-outputs", str(out)]
+        res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=str(ROOT))
+        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+        lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, res.stdout
+        return json.loads(lines[0])
+
+    import numpy as np
+
+    out = run(3, 1, tmp_path / "a")
+    assert out["unit"] == "images/s" and out["higher_is_better"] is True and out["dtype"] == "bf16"
+    assert out["metric"].startswith("images/sec (whole node) Qwen2-VL-2B")
+    assert out["steps"] == 3 and out["warmup"] == 1 and len(out["ms_of_each_step"]) == 3
+    assert abs(out["value"] - 64 / (out["ms_per_step"] / 1e3)) <= 1e-3 * out["value"]
+    assert out["roofline"]["launches"] > 0 and 0 < out["roofline"]["frac"] < 1
+    for k in ("batch_invariance_check", "eos_terminated", "real_image_sizes", "images_per_s_from_host_uint8", "label_cosine_per_sec",
+              "roofline_decode", "config2_qwen2vl_2b", "cpu_baseline", "box_calibration"):
+        assert k not in out, k
+    assert set(out["leg_seconds"]) == {"setup_weights_inputs", "warmup_and_timed_steps", "total_since_process_start"}
+    a = np.load(tmp_path / "a" / "tokens.npy")
+    assert a.dtype == np.float32 and a.shape == (64, 16)
+    assert np.array_equal(a, np.round(a)) and a.min() >= 0 and a.max() < 151936
+    run(1, 0, tmp_path / "b")
+    assert np.array_equal(np.load(tmp_path / "b" / "tokens.npy"), a)

@@ -12,7 +12,7 @@ set -u
 TAG=${1:-r06}
 WHAT=${2:-all}
 ROOT=$(pwd); export TMPDIR=/tmp; mkdir -p gpurun_out profiles
-COMMON="--no-cpu-baseline --no-big-legs --no-pil-leg"
+COMMON="--full --no-cpu-baseline --no-big-legs --no-pil-leg"
 cleanup() { rm -rf /tmp/prof_bench /tmp/pmc_${TAG}_bench_FETCH_SIZE /tmp/pmc_${TAG}_bench_WRITE_SIZE; }
 trap cleanup EXIT
 if [ $WHAT = trace ] || [ $WHAT = all ]; then

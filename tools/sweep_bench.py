@@ -24,7 +24,7 @@ for arg in sys.argv[1:]:
             extra = ["--steps", str(max(2, min(12, 1024 // int(v)))), "--warmup", "2"]
         else:
             extra = ["--steps", "2", "--warmup", "1"]
-        cmd = [sys.executable, str(ROOT / "bench.py"), "--model", model, "--no-cpu-baseline", "--no-pil-leg", "--scorer-labels", "4096",
+        cmd = [sys.executable, str(ROOT / "bench.py"), "--model", model, "--full", "--no-cpu-baseline", "--no-pil-leg", "--scorer-labels", "4096",
                FLAGS[name], v, *extra]
         res = subprocess.run(cmd, capture_output=True, text=True)
         line = [l for l in res.stdout.splitlines() if l.startswith("{")]
