@@ -247,6 +247,16 @@ int owc_argmax_bf16(owc_ctx* ctx, const void* logits, int64_t ld, int rows, int 
  * lmms_owc_amd/engine/beam.py. */
 int owc_beam_candidates(owc_ctx* ctx, const void* logits, int64_t ld, int rows, int vocab, int k, float* logz, float* top_val,
                         int32_t* top_idx, void* stream);
+/* The same step under HF's repetition penalty (owc_llm_set_repetition_penalty).  HF's beam search runs the logits processors on the
+ * LOG-SOFTMAX output, not on the raw logits as its greedy / sampled loops do, so per row (bitmap row row_slot[r], NULL: row r):
+ *   logz[r]                = as owc_beam_candidates (the same summation order: at penalty 1 the same bits)
+ *   lp                     = fp32(logits[r][v]) - logz[r];   v' = seen ? (lp < 0 ? lp * penalty : lp / penalty) : lp
+ *   top_val / top_idx[r][] = the k largest v' (PENALISED LOG-PROBABILITIES, not logits) and their ids, descending, the lowest id
+ *                            first among equal values
+ * 1 <= k <= 64, words_per_row * 32 >= vocab, penalty > 0. */
+int owc_beam_candidates_penalized(owc_ctx* ctx, const void* logits, int64_t ld, int rows, int vocab, int k, const uint32_t* seen,
+                                  int words_per_row, const int32_t* row_slot, float penalty, float* logz, float* top_val,
+                                  int32_t* top_idx, void* stream);
 /* out[r] = log softmax(logits[r])[target[r]] in fp32 (0 where target[r] < 0): the per-token terms of HF's causal-LM loss,
  * which LLaVA.loglikelihood averages (reference src/models/_llava_hf.py:243-245, outputs["loss"]). */
 int owc_token_logprob_bf16(owc_ctx* ctx, const void* logits, int64_t ld, const int32_t* target, int rows, int vocab, float* out,
@@ -434,6 +444,8 @@ int owc_llm_decode_step(owc_ctx* ctx, const owc_llm_weights* w, const owc_kv_cac
  *   slot of the launch), owc_llm_decode_step marks the token it is fed (slot[b]) - under teacher forcing the forced token, as HF's
  *   input_ids would hold - and both apply the penalty through the bitmap row of the sequence.  Greedy: exact fp32 arithmetic on
  *   the fly inside the argmax.  Sampled (`sampling` != NULL): the penalised values are written back as bf16 in front of the draw.
+ *   Beam search: the caller reads its candidates through owc_beam_candidates_penalized (HF penalises the log-probabilities there)
+ *   and copies a bitmap row wherever it copies a hypothesis's K / V rows.
  *   seen == NULL switches it off (the default).  Not applied in OWC_PREFILL_SCORE_ROWS mode (loglikelihood reads raw logits). */
 int owc_llm_set_repetition_penalty(owc_ctx* ctx, float penalty, uint32_t* seen, int words_per_row);
 /* the two pieces on their own (op-level tests): mark ids[t] in bitmap row slot[t] (slot NULL: row t); penalised greedy argmax of

@@ -16,7 +16,7 @@
 
 extern "C" {
 
-int owc_abi_version(void) { return 19; }
+int owc_abi_version(void) { return 20; }
 
 int owc_has_timing_knobs(void) {   // 1 only in libowc_hip_timing.so (tools/); the product library answers 0
 #ifdef OWC_TIMING_KNOBS
@@ -198,6 +198,19 @@ int owc_beam_candidates(owc_ctx* ctx, const void* logits, int64_t ld, int rows, 
   if (!ctx || !logits || !logz || !top_val || !top_idx) return OWC_ERR_ARG;
   if (rows <= 0 || vocab <= 0 || k <= 0 || k > vocab || k > 64) OWC_FAIL(ctx, OWC_ERR_SHAPE, "owc_beam_candidates: need 1 <= k <= min(64, vocab)");
   RET(ctx, "owc_beam_candidates", owc_launch_beam_candidates(logits, ld, rows, vocab, k, logz, top_val, top_idx, ST(stream)));
+}
+
+int owc_beam_candidates_penalized(owc_ctx* ctx, const void* logits, int64_t ld, int rows, int vocab, int k, const uint32_t* seen,
+                                  int words_per_row, const int32_t* row_slot, float penalty, float* logz, float* top_val,
+                                  int32_t* top_idx, void* stream) {
+  if (!ctx || !logits || !seen || !logz || !top_val || !top_idx) return OWC_ERR_ARG;
+  if (rows <= 0 || vocab <= 0 || k <= 0 || k > vocab || k > 64)
+    OWC_FAIL(ctx, OWC_ERR_SHAPE, "owc_beam_candidates_penalized: need 1 <= k <= min(64, vocab)");
+  if (words_per_row <= 0 || (int64_t)words_per_row * 32 < vocab)
+    OWC_FAIL(ctx, OWC_ERR_SHAPE, "owc_beam_candidates_penalized: repetition-penalty bitmap narrower than the vocabulary");
+  if (!(penalty > 0.f)) OWC_FAIL(ctx, OWC_ERR_ARG, "owc_beam_candidates_penalized: need penalty > 0");
+  RET(ctx, "owc_beam_candidates_penalized", owc_launch_beam_candidates_penalized(logits, ld, rows, vocab, k, seen, words_per_row, row_slot,
+                                                                                  penalty, logz, top_val, top_idx, ST(stream)));
 }
 
 int owc_sample_bf16(owc_ctx* ctx, const void* logits, int64_t ld, int rows, int vocab, const owc_sampling* sampling,

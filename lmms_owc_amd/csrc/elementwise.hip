@@ -751,6 +751,104 @@ __global__ __launch_bounds__(BEAM_T) void beam_candidates_kernel(const bf16_t* _
   }
 }
 
+// Beam search under HF's repetition penalty.  In `_beam_search` HF runs the logits processors on the LOG-SOFTMAX output
+// (`log_probs = logits_processor(input_ids, log_softmax(logits.float()))`), not on the raw logits as its greedy / sampled loops do:
+// every id the hypothesis has seen (bitmap row row_slot[row], NULL: row) gets lp < 0 ? lp * p : lp / p with lp = fp32(l) - logz.
+// Per row: logz exactly as beam_candidates_kernel computes it (the row max - order-free - then the same strided sums and the same
+// fixed tree, so at p = 1 it is the same bits), then K sweeps over the penalised log-probs, one bitmap word per 32 logits
+// (broadcast inside the wave: 32 neighbouring lanes read the same word).  Same picking rule as beam_candidates_kernel: the best
+// (value, id) lexicographically after the previous pick, the lowest id first among equal values.
+__global__ __launch_bounds__(BEAM_T) void beam_candidates_penalized_kernel(const bf16_t* __restrict__ logits, long ld, int V, int K,
+                                                                           const unsigned* __restrict__ seen, int wpr,
+                                                                           const int* __restrict__ row_slot, float penalty,
+                                                                           float* __restrict__ logz, float* __restrict__ top_val,
+                                                                           int* __restrict__ top_idx) {
+  __shared__ float sv[BEAM_T / 64];
+  __shared__ int si[BEAM_T / 64];
+  __shared__ float bcast_v;
+  __shared__ int bcast_i;
+  const int row = blockIdx.x, tid = threadIdx.x, w = tid >> 6;
+  const bf16_t* x = logits + (long)row * ld;
+  const unsigned* bits = seen + (long)(row_slot ? row_slot[row] : row) * wpr;
+  auto block_best = [&](float v, int i) {   // (max value, min id among equals) over the block -> bcast_v / bcast_i
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(v, o, 64);
+      const int oi = __shfl_xor(i, o, 64);
+      if (ov > v || (ov == v && oi < i)) {
+        v = ov;
+        i = oi;
+      }
+    }
+    __syncthreads();   // (the previous round's broadcast has been read by everybody)
+    if ((tid & 63) == 0) {
+      sv[w] = v;
+      si[w] = i;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      for (int k = 1; k < BEAM_T / 64; ++k)
+        if (sv[k] > v || (sv[k] == v && si[k] < i)) {
+          v = sv[k];
+          i = si[k];
+        }
+      bcast_v = v;
+      bcast_i = i;
+    }
+    __syncthreads();
+  };
+  // row max of the raw logits (the first pick of beam_candidates_kernel)
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int i = tid; i < V; i += BEAM_T) {
+    const float f = bf2f(x[i]);
+    if (f > best || (f == best && i < bi)) {
+      best = f;
+      bi = i;
+    }
+  }
+  block_best(best, bi);
+  const float row_max = bcast_v;
+  // log-sum-exp: per-thread strided sums, then a fixed tree (beam_candidates_kernel's order)
+  float s = 0.f;
+  for (int i = tid; i < V; i += BEAM_T) s += __expf(bf2f(x[i]) - row_max);
+  s = wave_sum(s);
+  __syncthreads();
+  if ((tid & 63) == 0) sv[w] = s;
+  __syncthreads();
+  if (tid == 0) {
+    float t = 0.f;
+    for (int k = 0; k < BEAM_T / 64; ++k) t += sv[k];
+    const float lz = row_max + __logf(t);
+    logz[row] = lz;
+    bcast_v = lz;
+  }
+  __syncthreads();
+  const float lz = bcast_v;
+  // the K largest penalised log-probs
+  float pv = INFINITY;
+  int pi = -1;
+  for (int k = 0; k < K; ++k) {
+    best = -INFINITY;
+    bi = 0x7fffffff;
+    for (int i = tid; i < V; i += BEAM_T) {
+      float f = bf2f(x[i]) - lz;
+      if ((bits[i >> 5] >> (i & 31)) & 1u) f = rep_penalize(f, penalty);
+      if ((f < pv || (f == pv && i > pi)) && (f > best || (f == best && i < bi))) {
+        best = f;
+        bi = i;
+      }
+    }
+    block_best(best, bi);
+    pv = bcast_v;
+    pi = bcast_i;
+    if (tid == 0) {
+      top_val[(long)row * K + k] = pv;
+      top_idx[(long)row * K + k] = pi;
+    }
+  }
+}
+
 // Decode bookkeeping (HF GenerationMixin greedy loop): finished sequences emit pad, EOS marks done.
 //   out_row (optional): row of out_tokens (and index into `forced`) that compact row b belongs to - after an EOS-aware
 //     row compaction the B live rows are a subset of the original batch (NULL: identity);
@@ -1066,6 +1164,14 @@ int owc_launch_token_logprob(const void* logits, long ld, const int* target, int
 int owc_launch_beam_candidates(const void* logits, long ld, int rows, int V, int K, float* logz, float* top_val, int* top_idx,
                                hipStream_t st) {
   hipLaunchKernelGGL(beam_candidates_kernel, dim3(rows), dim3(BEAM_T), 0, st, (const bf16_t*)logits, ld, V, K, logz, top_val, top_idx);
+  return hipGetLastError() == hipSuccess ? OWC_OK : OWC_ERR_HIP;
+}
+
+int owc_launch_beam_candidates_penalized(const void* logits, long ld, int rows, int V, int K, const unsigned* seen, int wpr,
+                                         const int* row_slot, float penalty, float* logz, float* top_val, int* top_idx, hipStream_t st) {
+  if (rows <= 0 || V <= 0 || K <= 0 || K > V || K > 64 || !seen || wpr * 32 < V || !(penalty > 0.f)) return OWC_ERR_SHAPE;
+  hipLaunchKernelGGL(beam_candidates_penalized_kernel, dim3(rows), dim3(BEAM_T), 0, st, (const bf16_t*)logits, ld, V, K, seen, wpr,
+                     row_slot, penalty, logz, top_val, top_idx);
   return hipGetLastError() == hipSuccess ? OWC_OK : OWC_ERR_HIP;
 }
 

@@ -66,6 +66,8 @@ int owc_launch_penalize_rows(void* logits, long ld, int rows, int V, const unsig
                              const int* row_index, float penalty, hipStream_t st);
 int owc_launch_beam_candidates(const void* logits, long ld, int rows, int V, int K, float* logz, float* top_val, int* top_idx,
                                hipStream_t st);
+int owc_launch_beam_candidates_penalized(const void* logits, long ld, int rows, int V, int K, const unsigned* seen, int wpr,
+                                         const int* row_slot, float penalty, float* logz, float* top_val, int* top_idx, hipStream_t st);
 int owc_launch_sample(const void* logits, long ld, int rows, int V, const owc_sampling* sp, const int* row_map, int step,
                       const int* step_state, int* out, hipStream_t st);
 int owc_launch_token_logprob(const void* logits, long ld, const int* target, int rows, int V, float* out, hipStream_t st);

@@ -1,5 +1,5 @@
 """Beam-search bookkeeping for the batched decoder (host side; the arithmetic - logits, log-sum-exp, per-row top candidates - is
-in libowc_hip.so: `owc_llm_decode_step`, `owc_beam_candidates`).
+in libowc_hip.so: `owc_llm_decode_step`, `owc_beam_candidates` / `owc_beam_candidates_penalized`).
 
 The reference passes `num_beams` from a request's gen_kwargs to HF's `generate` (/root/reference/src/models/_qwen2_vl.py:308-329,
 _llava_hf.py:365-376) with everything else at HF's defaults: `do_sample=False`, `length_penalty=1.0`, `early_stopping=False`, one
@@ -48,7 +48,8 @@ class BeamSearcher:
 
     def step(self, logz: np.ndarray, top_val: np.ndarray, top_idx: np.ndarray):
         """One step.  For every running row (prompt b, beam j): `logz[b, j]` = log-sum-exp of its logits, `top_val / top_idx[b, j, :]`
-        its 2 x num_beams largest logits (descending, lowest token id first among equals) and their token ids.  Returns
+        its 2 x num_beams largest logits (descending, lowest token id first among equals) and their token ids - or, under a repetition
+        penalty, logz = 0 and the 2 x num_beams largest PENALISED log-probabilities (`owc_beam_candidates_penalized`).  Returns
         (parent [B, k], token [B, k], more): running beam j of prompt b continues beam parent[b, j] with token[b, j]."""
         B, k, g = self.B, self.k, self.g
         K2 = 2 * k

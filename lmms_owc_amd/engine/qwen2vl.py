@@ -734,9 +734,17 @@ class Qwen2VLEngine:
             raise ValueError("image token count does not match the image embeddings")
         return pos_list, max_pos, img_index
 
-    def generate_beam(self, prompts: list, img_embeds: torch.Tensor | None, grids_per_prompt: list, max_new_tokens: int, num_beams: int,
-                      *, eos_token_id: int, pad_token_id: int = 0, img_rows: list | None = None, length_penalty: float = 1.0,
-                      early_stopping=False, return_scores: bool = False):
+    def generate_beam(self, *args, **kw):
+        """`_generate_beam_impl` (its docstring is the interface) with the context's repetition-penalty option cleared on every exit path."""
+        try:
+            return self._generate_beam_impl(*args, **kw)
+        finally:
+            self._lib.owc_llm_set_repetition_penalty(self._ctx, 1.0, None, 0)
+
+    def _generate_beam_impl(self, prompts: list, img_embeds: torch.Tensor | None, grids_per_prompt: list, max_new_tokens: int,
+                            num_beams: int, *, eos_token_id: int, pad_token_id: int = 0, img_rows: list | None = None,
+                            length_penalty: float = 1.0, early_stopping=False, return_scores: bool = False,
+                            repetition_penalty: float | None = None):
         """Beam search for a batch of prompts: what the reference asks HF for with `num_beams` > 1 in a request's gen_kwargs
         (/root/reference/src/models/_qwen2_vl.py:308-329, _llava_hf.py:365-376; `do_sample=False`, HF's `length_penalty=1.0`,
         `early_stopping=False`, the best hypothesis returned).  Every prompt is searched on its own, exactly as a batch-size-1
@@ -748,20 +756,28 @@ class Qwen2VLEngine:
         The KV cache follows the hypotheses by SLOT: a running beam that continues a parent takes over the parent's slot; when a
         parent is continued more than once, the extra children get a copy of its rows in the slot of a parent nobody continued.
         The prompt is prefilled once per prompt (the num_beams hypotheses start identical: HF gives all but the first a score of
-        -1e9 at the first step).  Returns int32 [B, max_new_tokens] (EOS kept, pad behind it) and optionally the scores."""
+        -1e9 at the first step).  Returns int32 [B, max_new_tokens] (EOS kept, pad behind it) and optionally the scores.
+
+        `repetition_penalty` (default: the engine's `self.repetition_penalty`, set by a model plug-in from the checkpoint's
+        generation_config.json; 1.0 = off): HF's beam search applies its logits processors to the LOG-SOFTMAX output, so every id of
+        a hypothesis's prompt (image placeholders included) and its own generated tokens gets lp < 0 ? lp * p : lp / p on its
+        log-probability before the candidates are ranked (`owc_beam_candidates_penalized`).  The seen-token bitmap has one row per
+        cache slot (the prefill marks the prompt, every decode step the token it is fed) and follows the hypotheses exactly as the
+        K / V rows do.  At 1.0 the step is `owc_beam_candidates`, unchanged."""
         from .beam import BeamSearcher
 
         d = self.d
         B, k = len(prompts), int(num_beams)
         if k < 2:
             raise ValueError("generate_beam is for num_beams >= 2 (one beam is `generate`)")
-        if float(self.repetition_penalty) != 1.0:
-            raise NotImplementedError("beam search with a repetition penalty (generation_config.json `repetition_penalty` != 1) is not "
-                                      "implemented by the HIP decoder; greedy and sampled one-beam generation are")
+        rep = float(self.repetition_penalty if repetition_penalty is None else repetition_penalty)
+        if not rep > 0:
+            raise ValueError("repetition_penalty must be > 0 (1.0 = off)")
         if B == 0:
             out = torch.empty((0, max_new_tokens), dtype=I32, device=self.device)
             return (out, np.zeros(0, np.float32)) if return_scores else out
         R = B * k                                   # (decode steps are launched directly: the rows' slots change between steps)
+        K2 = 2 * k                                  # candidates per running row
         lens = np.array([len(p) for p in prompts], dtype=np.int64)
         Hkv, G = d.n_kv_heads, d.n_q_heads // d.n_kv_heads
         s_max = (int(lens.max()) + max_new_tokens + 15) // 16 * 16
@@ -771,6 +787,19 @@ class Qwen2VLEngine:
         pos_list, max_pos, img_index = self._positions_and_image_rows(prompts, grids_per_prompt, img_embeds, img_rows)
         if int(max_pos.max()) + max_new_tokens + 1 > d.max_positions:
             raise ValueError("prompt + generation exceeds the rope table (raise Qwen2VLDims.max_positions)")
+        seen = None   # (held for the whole call: the context points at it until the `finally` of generate_beam)
+        if rep != 1.0:   # seen-token bitmap, one row per cache slot: the prefill marks prompt b in row b * k, a decode step the fed token
+            wpr = (d.vocab + 31) // 32
+            seen = torch.zeros((R, wpr), dtype=I32, device=self.device)
+            _lib.check(self._lib.owc_llm_set_repetition_penalty(self._ctx, rep, seen.data_ptr(), wpr), self.dev_index)
+
+        def candidates(lg, row_slot):
+            """(logz, top_val, top_idx) on the host for BeamSearcher.step; penalised: top_val holds log-probs already, logz = 0."""
+            if seen is None:
+                return tuple(x.cpu().numpy() for x in ops.beam_candidates(lg, K2))
+            _, tv_, ti_ = ops.beam_candidates_penalized(lg, K2, seen, rep, row_slot)
+            return np.zeros(lg.shape[0], np.float32), tv_.cpu().numpy(), ti_.cpu().numpy()
+
         # ---- prefill: prompt b into slot b * k (the slots of a prompt's beams are b * k .. b * k + k - 1)
         first_logits = torch.empty((B, d.vocab), dtype=BF16, device=self.device)
         next_tok = torch.empty(B, dtype=I32, device=self.device)
@@ -788,16 +817,16 @@ class Qwen2VLEngine:
         finally:
             self.share_prefix = share
         bs = BeamSearcher(B, k, max_new_tokens, eos_token_id, pad_token_id, length_penalty, early_stopping)
-        K2 = 2 * k
-        # step 0: every beam of a prompt sees the prefill's logits
-        logz, tv, ti = ops.beam_candidates(first_logits, K2)
-        logz, tv, ti = (x.cpu().numpy() for x in (logz, tv, ti))
-        parent, token, more = bs.step(np.repeat(logz[:, None], k, 1), np.repeat(tv[:, None], k, 1), np.repeat(ti[:, None], k, 1))
-        # all k running beams continue "beam 0" = the prompt: its cache rows go to the prompt's other slots
+        # step 0: every beam of a prompt sees the prefill's logits (and the bitmap row of slot b * k)
         base = torch.arange(B, device=self.device) * k
+        logz, tv, ti = candidates(first_logits, None if seen is None else base.to(I32))
+        parent, token, more = bs.step(np.repeat(logz[:, None], k, 1), np.repeat(tv[:, None], k, 1), np.repeat(ti[:, None], k, 1))
+        # all k running beams continue "beam 0" = the prompt: its cache rows (and bitmap row) go to the prompt's other slots
         for j in range(1, k):
             for t5 in kv5:
                 t5[:, base + j, :, : int(lens.max())] = t5[:, base, :, : int(lens.max())]
+            if seen is not None:
+                seen[base + j] = seen[base]
         slot = (np.arange(B)[:, None] * k + np.arange(k)[None, :]).astype(np.int64)            # slot of running beam [b, j]
         ar = np.arange(R, dtype=np.int64)
         q_start, o_start = self._i32(ar * (d.n_q_heads + 2 * Hkv)), self._i32(ar * d.n_q_heads)
@@ -823,8 +852,7 @@ class Qwen2VLEngine:
                 done.data_ptr(), scratch_tok.data_ptr(), 1, 0, None, R, -1, -1, pad_token_id, None, None, None,
                 logits.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr())
             _lib.check(rc, self.dev_index)
-            logz, tv, ti = ops.beam_candidates(logits, K2)
-            logz, tv, ti = (x.cpu().numpy() for x in (logz, tv, ti))
+            logz, tv, ti = candidates(logits, dev[2])      # (bitmap row = the beam's slot, which the step just marked its token in)
             parent, token, more = bs.step(logz.reshape(B, k), tv.reshape(B, k, K2), ti.reshape(B, k, K2))
             g += 1
             if not more:
@@ -850,6 +878,8 @@ class Qwen2VLEngine:
                 d_t = torch.tensor(dst, device=self.device)
                 for t5 in kv5:
                     t5[:, d_t, :, :rows_now] = t5[:, s_t, :, :rows_now]
+                if seen is not None:   # whole rows, overwritten: a destination slot is one no beam continued
+                    seen[d_t] = seen[s_t]
             slot = new_slot
         toks, scores = bs.result()
         out = torch.from_numpy(toks.astype(np.int32)).to(self.device)

@@ -661,7 +661,9 @@ def pass_key(max_new: int, sampling: dict | None, num_beams: int = 1) -> tuple:
 
 
 def beams_from_gen_kwargs(gen_kwargs: dict) -> int:
-    """`num_beams` of a request (reference src/models/_qwen2_vl.py:308-329, _llava_hf.py:355-376: default 1, handed to HF's generate)."""
+    """`num_beams` of a request (reference src/models/_qwen2_vl.py:308-329, _llava_hf.py:355-376: default 1, handed to HF's generate).
+    Beams run under the engine's `repetition_penalty` (the checkpoint's generation_config.json value, which HF merges into the same
+    call), applied to the log-probabilities as HF's beam search does: `Qwen2VLEngine.generate_beam`."""
     k = int(gen_kwargs.get("num_beams", 1) or 1)
     if k < 1:
         raise ValueError("num_beams must be >= 1")

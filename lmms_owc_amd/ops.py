@@ -194,6 +194,19 @@ def beam_candidates(logits, k: int):
     return logz, top_val, top_idx
 
 
+def beam_candidates_penalized(logits, k: int, seen, penalty: float, row_slot=None):
+    """`beam_candidates` under HF's repetition penalty, applied to the LOG-PROBABILITIES as HF's beam search does: ids marked in bitmap
+    row row_slot[r] (None: r) of `seen` [slots, words >= vocab / 32] get lp < 0 ? lp * p : lp / p.  Returns (logz float32 [rows],
+    top_val float32 [rows, k] = the k largest penalised log-probs, top_idx int32 [rows, k]): `owc_beam_candidates_penalized`."""
+    rows = logits.shape[0]
+    logz = torch.empty((rows,), dtype=F32, device=logits.device)
+    top_val = torch.empty((rows, k), dtype=F32, device=logits.device)
+    top_idx = torch.empty((rows, k), dtype=I32, device=logits.device)
+    _call("owc_beam_candidates_penalized", _dev(logits), logits.data_ptr(), logits.stride(0), rows, logits.shape[1], int(k),
+          seen.data_ptr(), seen.shape[1], _lib.ptr(row_slot), float(penalty), logz.data_ptr(), top_val.data_ptr(), top_idx.data_ptr())
+    return logz, top_val, top_idx
+
+
 def sample_bf16(logits, temperature: float, top_k: int = 0, top_p: float | None = None, seed: int = 0, stream_ids=None, row_map=None,
                 step: int = 0):
     """One draw per row of bf16 logits [rows, vocab] by owc_sampling (HF temperature -> top-k -> top-p -> multinomial; the library's
