@@ -62,7 +62,8 @@ const char* owc_last_error(const owc_ctx* ctx);
  * ping-pong only, 2 / negative = default: the bf16 and the fp8 ping-pong kernels), "prefill_prune_last" (0: owc_llm_prefill runs the last layer's attention /
  * o-proj / MLP on every row instead of the last-token rows only -- same logits bit for bit, tested), "bert_bf16x3" (0:
  * owc_bert_embed runs its linears on the exact f32-input MFMA instead of the three-piece bf16 split), "decode_fuse" (0: a
- * decode step runs mrope_kv + the generic attention kernel instead of owc_decode_attention), "decode_attn_nbuf1" (block count above
+ * decode step runs mrope_kv + the generic attention kernel instead of owc_decode_attention; with an fp8 KV cache the step then
+ * returns OWC_STATUS_ERR_SHAPE: only the fused kernel reads that cache), "decode_attn_nbuf1" (block count above
  * which the fused decode attention single-buffers V), "decode_norm_fuse" (rows up to which the decoder's RMSNorm is fused into the
  * qkv / gate-up skinny GEMM: 0 off, default 2, at most 4 -- same bits, tested), "gemm_skinny_deep" (0: no 9-deep ring for the long-K
  * skinny launches), "gemm_small_tiles" (the 64x64-tile kernel's 64x32 / 32x32 shapes for launches that cannot fill the chip: 0 off,
@@ -165,10 +166,15 @@ int owc_mrope_kv_write(owc_ctx* ctx, void* qkv, int64_t ld, const int32_t* pos3,
  * caches: [slot][n_kv][s_max][128]; out: [B][n_q * 128].  Equals owc_mrope_kv_write + owc_attention_bf16 in the decode
  * mapping: identical cache rows, attention output within the rounding of P (the four waves of a block split the keys and merge
  * their partial softmax results in a fixed order).  Replaces HF apply_multimodal_rotary_pos_emb (:180-222), the cache
- * update and Qwen2VLAttention's sdpa (:508-556) for a generated token. */
+ * update and Qwen2VLAttention's sdpa (:508-556) for a generated token.
+ * kv_dtype OWC_KV_FP8 (OWC_KV_BF16: k_scale / v_scale unused, NULL): the caches hold e4m3fn codes [slot][n_kv][s_max][128] and
+ * k_scale / v_scale [slot][n_kv][s_max] the row scales (owc_kv_cache); the fed token's rotated k row and v row are quantised
+ * as owc_quantize_rows_fp8 would, stored, and read back with the rest: softmax(q . (codes * k_scale)) . (codes * v_scale), the
+ * K scale applied to the fp32 score, the V scale to P before P is rounded to bf16.  ldo % 8 == 0. */
 int owc_decode_attention(owc_ctx* ctx, const void* qkv, int64_t ld, const int32_t* pos, const float* cos_t, const float* sin_t,
                          void* k_cache, void* v_cache, const int32_t* slot, const int32_t* write_idx, const int32_t* k_len,
-                         void* out, int64_t ldo, int B, int n_q_heads, int n_kv_heads, int s_max, float scale, void* stream);
+                         void* out, int64_t ldo, int B, int n_q_heads, int n_kv_heads, int s_max, float scale, int kv_dtype,
+                         float* k_scale, float* v_scale, void* stream);
 
 /* softmax(Q K^T * scale [+ causal mask]) V for packed variable-length sequences (flash-style).
  * Element (seq b, head h, row i, dim d) lives at
@@ -374,11 +380,37 @@ typedef struct owc_llm_weights {
                                     lm_head stay bf16; activations are quantised per token in front of every fp8 projection) */
 } owc_llm_weights;
 
+/* KV cache.  The fields after s_max were appended for the fp8 cache: a zero-initialised tail is the bf16 cache.
+ * dtype OWC_KV_FP8 (kv_dtype=fp8; needs head_dim 128 and n_q_heads / n_kv_heads <= 16, i.e. the fused decode attention):
+ *   k / v hold OCP e4m3fn codes (uint8) in the same layout; k_scale / v_scale hold one fp32 scale per (token, kv head) row,
+ *   float [n_layers][n_slots][n_kv_heads][s_max].  A row's scale and codes are owc_quantize_rows_fp8 of its head_dim values
+ *   (oracle/fp8_np.py quantize_rows: amax / 448, 1 for a zero row; RNE, saturating); K is quantised AFTER RoPE.  A K row costs
+ *   132 B instead of 256 B.
+ *   k_stage / v_stage: caller-owned bf16 buffers shaped like ONE layer of the bf16 cache, [n_slots][n_kv_heads][s_max][head_dim],
+ *   used by owc_llm_prefill only: every layer writes its rotated K / V rows there, prefill attention reads them there (so the
+ *   first-token logits are bit-identical to the bf16 cache's), and owc_kv_quantize_fp8 then quantises the rows the launch wrote
+ *   into that layer of the fp8 cache.
+ *   CONTRACT: with an fp8 cache a prefill launch attends only keys written by that same launch (plain prompts; shared-prefix
+ *   launches, whose prefix segment is part of the launch; OWC_PREFILL_SCORE_ROWS).  A decode step attends dequantised keys
+ *   only, the fed token's own row included (it is quantised, stored and read back by the step). */
+#define OWC_KV_BF16 0
+#define OWC_KV_FP8 1
 typedef struct owc_kv_cache {
-  void* k; /* [n_layers][n_slots][n_kv_heads][s_max][head_dim] bf16 */
+  void* k; /* [n_layers][n_slots][n_kv_heads][s_max][head_dim] bf16 (OWC_KV_FP8: uint8 e4m3fn codes) */
   void* v;
   int32_t n_slots, s_max;
+  int32_t dtype;             /* OWC_KV_BF16 | OWC_KV_FP8 */
+  float *k_scale, *v_scale;  /* OWC_KV_FP8: [n_layers][n_slots][n_kv_heads][s_max] */
+  void *k_stage, *v_stage;   /* OWC_KV_FP8: bf16 [n_slots][n_kv_heads][s_max][head_dim], prefill staging */
 } owc_kv_cache;
+
+/* Quantise the K / V rows one prefill launch wrote into the bf16 staging layer into ONE layer of an fp8 cache (k8 / v8 / k_scale /
+ * v_scale point at that layer): for every token t and kv head the row [(tok_slot[t] * n_kv_heads + kvh) * s_max + tok_idx[t]];
+ * rows with tok_slot[t] < 0 (shared prefix) are read from slot bcast_first_slot and written to every slot of
+ * [bcast_first_slot, + bcast_n_slots).  head_dim 128.  Codes and scales equal owc_quantize_rows_fp8 of the staged rows. */
+int owc_kv_quantize_fp8(owc_ctx* ctx, const void* k_stage, const void* v_stage, void* k8, void* v8, float* k_scale, float* v_scale,
+                        const int32_t* tok_slot, const int32_t* tok_idx, int T, int n_kv_heads, int s_max, int bcast_first_slot,
+                        int bcast_n_slots, void* stream);
 
 size_t owc_llm_workspace_bytes(const owc_llm_weights* w, int T, int n_seq);
 

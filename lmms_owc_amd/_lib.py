@@ -21,7 +21,7 @@ _lib: C.CDLL | None = None
 _ctx: dict[int, C.c_void_p] = {}
 _timing_ok = False
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 EPI_NONE, EPI_QUICK_GELU, EPI_GELU_ERF, EPI_RESIDUAL, EPI_SWIGLU, EPI_F32 = range(6)
 
@@ -79,8 +79,14 @@ WEIGHTS_BF16, WEIGHTS_FP8 = 0, 1
 PREFILL_LAST_TOKENS, PREFILL_SCORE_ROWS = 0, 1   # owc_llm_prefill score_mode
 
 
+KV_BF16, KV_FP8 = 0, 1   # owc_kv_cache.dtype
+
+
 class KvCache(C.Structure):
-    _fields_ = [("k", vp), ("v", vp), ("n_slots", C.c_int32), ("s_max", C.c_int32)]
+    """owc_kv_cache.  ``KvCache(k, v, n_slots, s_max)`` is the bf16 cache; the fp8 cache (e4m3fn codes in k / v) adds dtype = KV_FP8,
+    the per-row scales and the bf16 prefill staging layer (include/owc.h)."""
+    _fields_ = [("k", vp), ("v", vp), ("n_slots", C.c_int32), ("s_max", C.c_int32), ("dtype", C.c_int32),
+                ("k_scale", vp), ("v_scale", vp), ("k_stage", vp), ("v_stage", vp)]
 
 
 class Sampling(C.Structure):
@@ -119,7 +125,8 @@ SIGNATURES: dict[str, tuple] = {
     "owc_rope_table": (i32, [vp, vp, vp, i32, i32, i32, f32, i32, vp]),
     "owc_vision_rope": (i32, [vp, vp, i64, vp, vp, vp, i32, i32, i32, vp]),
     "owc_mrope_kv_write": (i32, [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
-    "owc_decode_attention": (i32, [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, vp]),
+    "owc_decode_attention": (i32, [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, i32, vp, vp, vp]),
+    "owc_kv_quantize_fp8": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "owc_attention_bf16": (i32, [vp, vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp,
                                  i32, i32, i32, i32, i32, i32, f32, vp]),
     "owc_quantize_rows_fp8": (i32, [vp, vp, i64, vp, i64, vp, i32, i32, vp]),

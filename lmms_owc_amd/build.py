@@ -108,17 +108,19 @@ def _lint_twins(funcs: dict[str, list[str]]) -> list[str]:
 
     hits = []
     for rx in TWIN_KERNELS:
-        mixes = {}
+        families = collections.defaultdict(dict)   # twins differ in the matched parameter only (bf16-cache and fp8-cache forms: two families)
         for fn, body in funcs.items():
             if rx.search(fn):
                 ops = [ln.split("//")[0].split() for ln in body]
-                mixes[fn] = collections.Counter(o[0] for o in ops if o and _FP_OPS.match(o[0]) and "_u32" not in o[0] and "_i32" not in o[0])
-        names = sorted(mixes)
-        for other in names[1:]:
-            if mixes[other] != mixes[names[0]]:
-                delta = {k: (mixes[names[0]][k], mixes[other][k]) for k in set(mixes[names[0]]) | set(mixes[other])
-                         if mixes[names[0]][k] != mixes[other][k]}
-                hits.append(f"{names[0]} and {other} must be bit-identical but their floating-point instruction mixes differ: {delta}")
+                families[rx.sub("", fn)][fn] = collections.Counter(
+                    o[0] for o in ops if o and _FP_OPS.match(o[0]) and "_u32" not in o[0] and "_i32" not in o[0])
+        for mixes in families.values():
+            names = sorted(mixes)
+            for other in names[1:]:
+                if mixes[other] != mixes[names[0]]:
+                    delta = {k: (mixes[names[0]][k], mixes[other][k]) for k in set(mixes[names[0]]) | set(mixes[other])
+                             if mixes[names[0]][k] != mixes[other][k]}
+                    hits.append(f"{names[0]} and {other} must be bit-identical but their floating-point instruction mixes differ: {delta}")
     return hits
 
 

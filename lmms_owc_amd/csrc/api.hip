@@ -16,7 +16,7 @@
 
 extern "C" {
 
-int owc_abi_version(void) { return 20; }
+int owc_abi_version(void) { return 21; }
 
 int owc_has_timing_knobs(void) {   // 1 only in libowc_hip_timing.so (tools/); the product library answers 0
 #ifdef OWC_TIMING_KNOBS
@@ -174,11 +174,23 @@ int owc_attention_bf16(owc_ctx* ctx, const void* Q, int64_t q_ts, int64_t q_hs, 
 
 int owc_decode_attention(owc_ctx* ctx, const void* qkv, int64_t ld, const int32_t* pos, const float* cos_t, const float* sin_t,
                          void* k_cache, void* v_cache, const int32_t* slot, const int32_t* write_idx, const int32_t* k_len,
-                         void* out, int64_t ldo, int B, int n_q_heads, int n_kv_heads, int s_max, float scale, void* stream) {
+                         void* out, int64_t ldo, int B, int n_q_heads, int n_kv_heads, int s_max, float scale, int kv_dtype,
+                         float* k_scale, float* v_scale, void* stream) {
   if (!ctx || !qkv || !pos || !cos_t || !sin_t || !k_cache || !v_cache || !slot || !write_idx || !k_len || !out) return OWC_ERR_ARG;
+  if (kv_dtype != OWC_KV_BF16 && kv_dtype != OWC_KV_FP8) OWC_FAIL(ctx, OWC_ERR_ARG, "owc_decode_attention: kv_dtype must be OWC_KV_BF16 or OWC_KV_FP8");
+  if (kv_dtype == OWC_KV_FP8 && (!k_scale || !v_scale)) OWC_FAIL(ctx, OWC_ERR_ARG, "owc_decode_attention: an fp8 cache needs k_scale and v_scale");
   RET(ctx, "owc_decode_attention",
       owc_launch_attn_decode_fused(qkv, ld, pos, cos_t, sin_t, k_cache, v_cache, slot, write_idx, k_len, out, ldo, B, n_q_heads,
-                                   n_kv_heads, s_max, scale, ST(stream)));
+                                   n_kv_heads, s_max, scale, ST(stream), kv_dtype == OWC_KV_FP8, k_scale, v_scale));
+}
+
+int owc_kv_quantize_fp8(owc_ctx* ctx, const void* k_stage, const void* v_stage, void* k8, void* v8, float* k_scale, float* v_scale,
+                        const int32_t* tok_slot, const int32_t* tok_idx, int T, int n_kv_heads, int s_max, int bcast_first_slot,
+                        int bcast_n_slots, void* stream) {
+  if (!ctx || !k_stage || !v_stage || !k8 || !v8 || !k_scale || !v_scale || !tok_slot || !tok_idx) return OWC_ERR_ARG;
+  RET(ctx, "owc_kv_quantize_fp8",
+      owc_launch_kv_quant_fp8(k_stage, v_stage, k8, v8, k_scale, v_scale, tok_slot, tok_idx, T, n_kv_heads, s_max, bcast_first_slot,
+                              bcast_n_slots, ST(stream)));
 }
 
 int owc_embed_tokens(owc_ctx* ctx, const int32_t* ids, const int32_t* img_index, const void* table,

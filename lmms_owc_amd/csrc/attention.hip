@@ -1104,14 +1104,38 @@ int launch(const void* Q, long q_ts, long q_hs, const void* K, long k_ts, long k
 // plain 1-D rope), Qwen2VLAttention.forward (:508-556).
 // ------------------------------------------------------------------------------------------------------------------------
 constexpr int DEC_VTILE = KB * 256;  // one V tile: 64 keys x 256 B
+constexpr int DEC_VTILE8 = KB * 128; // the same tile of an fp8 cache: 64 keys x 128 B
+constexpr int DEC_MERGE = 4 * 34 * 64 * 4;  // the merge image [4 waves][34 values][64 lanes] (larger than four 8 KiB tiles)
 
-template <int NBUF>   // V tiles per wave in LDS: 2 = the next tile is fetched under the current one (128 KiB per block: one block per CU, the
+// four e4m3fn codes (one dword) -> four bf16 (exact: every e4m3 value is a bf16 value; the f32 of a code has <= 3 mantissa bits)
+__device__ __forceinline__ u32x2 e4m3x4_to_bf16x4(unsigned dw) {
+  const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)dw, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)dw, true);
+  return (u32x2){(__float_as_uint(lo[0]) >> 16) | (__float_as_uint(lo[1]) & 0xffff0000u),
+                 (__float_as_uint(hi[0]) >> 16) | (__float_as_uint(hi[1]) & 0xffff0000u)};
+}
+__device__ __forceinline__ unsigned pack_bf16_hi(float a, float b) {   // (bf16(a), bf16(b)) of two exactly representable values
+  return (__float_as_uint(a) >> 16) | (__float_as_uint(b) & 0xffff0000u);
+}
+
+// FP8 (kv_dtype = fp8, include/owc.h owc_kv_cache): the cache holds e4m3fn codes [row][128] and one fp32 scale per (token, kv head)
+// row, quantised as owc_quantize_rows_fp8 quantises a row (scale = amax / 448, 1 for a zero row; RNE, saturating).  Same structure;
+// what differs:
+//   * the owner of the last tile quantises the fed token's rotated k row and its v row (lanes 0-7: k, lanes 16-31: v, absmax by an
+//     xor butterfly) and stores codes + scale; the new key is read back like every other one, so a step attends dequantised keys only;
+//   * K codes go global -> registers 16 bytes at a time and are expanded to bf16 for the bf16 MFMA: a lane's k-steps cover the dims
+//     16 g + 8 (ks & 1) + 64 (ks >> 1) + 0..7, and the Q fragments follow (a rotary pair is still k-steps ks and ks + 2 of one lane);
+//   * the per-key K scale multiplies the fp32 score column, the per-key V scale multiplies P before P is rounded to bf16;
+//   * V tiles are 8 KiB of codes, read with the SAME 16-bit transposing LDS read: a 16-bit element is a pair of adjacent dims of one
+//     key, so a lane receives 4 keys x (dim 2 i, dim 2 i + 1); expanded, the even and the odd dims are the A operands of two MFMAs
+//     whose output rows j are the dims 32 c + 2 j and 32 c + 2 j + 1 - undone where O is stored.  32-byte blocks of a row are
+//     XOR-swizzled with (key >> 1) & 3: the 8 keys x 32 B a 32-lane half reads fall on 64 distinct banks.
+template <int NBUF, bool FP8 = false>   // V tiles per wave in LDS: 2 = the next tile is fetched under the current one (128 KiB per block: one block per CU, the
                       // small-batch form), 1 = 64 KiB per block, two blocks = eight streaming waves per CU (large batches: HBM-bound)
 __global__ __launch_bounds__(256) void attn_decode_fused_kernel(
     const bf16_t* __restrict__ qkv, long ld, const int* __restrict__ pos, const float* __restrict__ cos_t,
     const float* __restrict__ sin_t, bf16_t* __restrict__ kc, bf16_t* __restrict__ vc, const int* __restrict__ slot,
     const int* __restrict__ write_idx, const int* __restrict__ k_len, bf16_t* __restrict__ O, long ldo, int n_q, int n_kv,
-    int s_max, float scale_log2e) {
+    int s_max, float scale_log2e, float* __restrict__ ksc = nullptr, float* __restrict__ vsc = nullptr) {
   // The two instantiations (NBUF 1 / 2) must give the SAME BITS: a decode batch that shrinks (EOS-aware row compaction) crosses
   // from one to the other in the middle of a sequence.  Under -ffp-contract=fast the compiler decided per instantiation which
   // mul + add pairs become an fma (round 4: the disassemblies differed by one v_fma_f32 / v_sub_f32, and ~1 % of the row-steps of
@@ -1133,11 +1157,66 @@ __global__ __launch_bounds__(256) void attn_decode_fused_kernel(
   const int ntiles = (L + KB - 1) / KB;
   const bf16_t* tok = qkv + (long)b * ld;
   const long trow = (long)pos[b] * 64;          // rope table row of the fed token
+  uint8_t* K8 = (uint8_t*)kc + row0 * 128;      // FP8: codes and row scales of this (sequence, kv head)
+  uint8_t* V8 = (uint8_t*)vc + row0 * 128;
+  float* Ks = ksc + row0;
+  float* Vs = vsc + row0;
 
   // ---- the owner of the last tile: rope(k), cache write of k and v (lanes 0-7: one rotary pair of 8-dim chunks each; lanes 8-23: v)
   // (widx < s_max: a finished row that the caller has not dropped yet keeps advancing its write index; it must never write into
   //  the next slot - the host compacts such rows away before that, this is the second line of defence)
-  if (w == ((ntiles - 1) & 3) && widx < s_max) {
+  if (FP8 && w == ((ntiles - 1) & 3) && widx < s_max) {
+    bf16x8 oa, ob;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) oa[e] = ob[e] = f2bf(0.f);
+    if (l < 8) {
+      const bf16_t* kp = tok + (long)(n_q + hk) * 128;
+      const bf16x8 a = *(const bf16x8*)(kp + l * 8), bb = *(const bf16x8*)(kp + l * 8 + 64);
+      const f32x4 c0 = *(const f32x4*)(cos_t + trow + l * 8), c1 = *(const f32x4*)(cos_t + trow + l * 8 + 4);
+      const f32x4 s0 = *(const f32x4*)(sin_t + trow + l * 8), s1 = *(const f32x4*)(sin_t + trow + l * 8 + 4);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float c = e < 4 ? c0[e & 3] : c1[e & 3], sn = e < 4 ? s0[e & 3] : s1[e & 3];
+        const float x1 = bf2f(a[e]), x2 = bf2f(bb[e]);
+        oa[e] = f2bf(rbf(x1 * c) + rbf(-x2 * sn));
+        ob[e] = f2bf(rbf(x2 * c) + rbf(x1 * sn));
+      }
+    } else if (l >= 16 && l < 32) {
+      oa = *(const bf16x8*)(tok + (long)(n_q + n_kv + hk) * 128 + (l - 16) * 8);
+    }
+    // row absmax: lanes 0-7 hold the k row, lanes 16-31 the v row, every other lane zeros (xor 8 pairs the k lanes with zeros)
+    float amax = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fmaxf(fabsf(bf2f(oa[e])), fabsf(bf2f(ob[e]))));
+#pragma unroll
+    for (int o_ = 1; o_ <= 8; o_ <<= 1) amax = fmaxf(amax, __shfl_xor(amax, o_, 64));
+    const float qscale = amax > 0.f ? amax / 448.0f : 1.0f;   // quant_rows_fp8_kernel's arithmetic
+    float qa[8], qb[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      qa[e] = fminf(fmaxf(bf2f(oa[e]) / qscale, -448.0f), 448.0f);
+      qb[e] = fminf(fmaxf(bf2f(ob[e]) / qscale, -448.0f), 448.0f);
+    }
+    int ca[2] = {0, 0}, cb[2] = {0, 0};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      ca[h] = __builtin_amdgcn_cvt_pk_fp8_f32(qa[4 * h], qa[4 * h + 1], ca[h], false);
+      ca[h] = __builtin_amdgcn_cvt_pk_fp8_f32(qa[4 * h + 2], qa[4 * h + 3], ca[h], true);
+      cb[h] = __builtin_amdgcn_cvt_pk_fp8_f32(qb[4 * h], qb[4 * h + 1], cb[h], false);
+      cb[h] = __builtin_amdgcn_cvt_pk_fp8_f32(qb[4 * h + 2], qb[4 * h + 3], cb[h], true);
+    }
+    if (l < 8) {
+      uint8_t* dst = K8 + (long)widx * 128;
+      *(int2*)(dst + l * 8) = make_int2(ca[0], ca[1]);
+      *(int2*)(dst + l * 8 + 64) = make_int2(cb[0], cb[1]);
+      if (l == 0) Ks[widx] = qscale;
+    } else if (l >= 16 && l < 32) {
+      *(int2*)(V8 + (long)widx * 128 + (l - 16) * 8) = make_int2(ca[0], ca[1]);
+      if (l == 16) Vs[widx] = qscale;
+    }
+    __builtin_amdgcn_s_waitcnt(0);   // codes and scales are in L2 before this wave's tile loads are issued
+  }
+  if (!FP8 && w == ((ntiles - 1) & 3) && widx < s_max) {
     if (l < 8) {
       const bf16_t* kp = tok + (long)(n_q + hk) * 128;
       const bf16x8 a = *(const bf16x8*)(kp + l * 8), bb = *(const bf16x8*)(kp + l * 8 + 64);
@@ -1166,10 +1245,10 @@ __global__ __launch_bounds__(256) void attn_decode_fused_kernel(
   {
     const bf16_t* qp = tok + (long)(hk * G + min(fr, G - 1)) * 128;
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const bf16x8*)(qp + (ks * 4 + g) * 8);
+    for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const bf16x8*)(qp + (FP8 ? (ks >> 1) * 64 + g * 16 + (ks & 1) * 8 : (ks * 4 + g) * 8));
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {   // chunk c = 4 ks + g < 8 pairs with chunk c + 8 = k-step ks + 2, same lane
-      const int i0 = (ks * 4 + g) * 8;
+    for (int ks = 0; ks < 2; ++ks) {   // chunk c = 4 ks + g < 8 pairs with chunk c + 8 = k-step ks + 2, same lane (FP8: dims 16 g + 8 ks)
+      const int i0 = FP8 ? g * 16 + ks * 8 : (ks * 4 + g) * 8;
       const f32x4 c0 = *(const f32x4*)(cos_t + trow + i0), c1 = *(const f32x4*)(cos_t + trow + i0 + 4);
       const f32x4 s0 = *(const f32x4*)(sin_t + trow + i0), s1 = *(const f32x4*)(sin_t + trow + i0 + 4);
       bf16x8 oa, ob;
@@ -1190,11 +1269,21 @@ __global__ __launch_bounds__(256) void attn_decode_fused_kernel(
   for (int d = 0; d < C::DT; ++d) o[d] = (f32x4){0.f, 0.f, 0.f, 0.f};
   float mrun = -1e30f, lrun = 0.f;
 
-  char* vbuf = lds + w * (NBUF * DEC_VTILE);
+  constexpr int VT = FP8 ? DEC_VTILE8 : DEC_VTILE;
+  char* vbuf = lds + w * (NBUF * VT);
   // V tile t -> this wave's LDS buffer: 16 pieces of 1 KiB (4 keys x 256 B each), rows clamped at the ragged end, the 16-byte
   // chunk order of a row XOR-swizzled with (key & 7) << 1 like the block-staged kernel above
   auto stage_v = [&](int buf, int t) {
-    char* base = vbuf + buf * DEC_VTILE;
+    char* base = vbuf + buf * VT;
+    if constexpr (FP8) {   // 8 pieces of 1 KiB (8 keys x 128 B), 16-byte chunk order XOR-swizzled with ((key >> 1) & 3) << 1
+#pragma unroll
+      for (int p = 0; p < 8; ++p) {
+        const int key = p * 8 + (l >> 3), posc = l & 7;
+        const int c = posc ^ (((key >> 1) & 3) << 1);
+        glds16(V8 + (long)min(t * KB + key, L - 1) * 128 + c * 16, base + p * 1024);
+      }
+      return;
+    }
 #pragma unroll
     for (int p = 0; p < 16; ++p) {
       const int key = p * 4 + (l >> 4), posc = l & 15;
@@ -1204,7 +1293,26 @@ __global__ __launch_bounds__(256) void attn_decode_fused_kernel(
     }
   };
   bf16x8 kf[4][4];
+  u32x4 kraw[4][2];            // FP8: the codes of a lane's 32 dims per key, expanded into kf in front of the MFMAs
+  float ksv[4][4], vsv[4][4];  // FP8: K / V row scales of the keys 16 kt + 4 g + r (the rows of this lane's score registers)
   auto load_k = [&](int t) {   // K fragments of tile t: lane (fr, g) <- key 16 kt + fr, chunk 4 ks + g
+    if constexpr (FP8) {
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt) {
+        const uint8_t* kr = K8 + (long)min(t * KB + kt * 16 + fr, L - 1) * 128 + g * 16;
+        kraw[kt][0] = *(const u32x4*)kr;
+        kraw[kt][1] = *(const u32x4*)(kr + 64);
+      }
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int key = min(t * KB + kt * 16 + g * 4 + r, L - 1);
+          ksv[kt][r] = Ks[key];
+          vsv[kt][r] = Vs[key];
+        }
+      return;
+    }
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) {
       const bf16_t* kr = Kseq + (long)min(t * KB + kt * 16 + fr, L - 1) * 128 + g * 8;
@@ -1227,11 +1335,26 @@ __global__ __launch_bounds__(256) void attn_decode_fused_kernel(
     else if (t + 4 < ntiles) stage_v(buf ^ 1, t + 4);
     // ---- S^T = K . Q^T (waits for the K fragments only: the V tiles may still fly)
     f32x4 s[4];
+    if constexpr (FP8) {
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+          const u32x2 e0 = e4m3x4_to_bf16x4(kraw[kt][ks >> 1][2 * (ks & 1)]), e1 = e4m3x4_to_bf16x4(kraw[kt][ks >> 1][2 * (ks & 1) + 1]);
+          kf[kt][ks] = __builtin_bit_cast(bf16x8, ((u32x4){e0[0], e0[1], e1[0], e1[1]}));
+        }
+    }
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) {
       s[kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kt][ks], qf[ks], s[kt], 0, 0, 0);
+    }
+    if constexpr (FP8) {   // dequantise the score column of every key
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) s[kt][r] *= ksv[kt][r];
     }
     if (t * KB + KB > L) {   // ragged last tile (wave-uniform branch)
       asm volatile("" ::: "memory");
@@ -1274,17 +1397,48 @@ __global__ __launch_bounds__(256) void attn_decode_fused_kernel(
     for (int sx = 0; sx < 2; ++sx)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        pf[sx][r] = f2bf(x[2 * sx][r]);
-        pf[sx][4 + r] = f2bf(x[2 * sx + 1][r]);
+        if constexpr (FP8) {   // the V row scale goes into P before P is rounded
+          pf[sx][r] = f2bf(x[2 * sx][r] * vsv[2 * sx][r]);
+          pf[sx][4 + r] = f2bf(x[2 * sx + 1][r] * vsv[2 * sx + 1][r]);
+        } else {
+          pf[sx][r] = f2bf(x[2 * sx][r]);
+          pf[sx][4 + r] = f2bf(x[2 * sx + 1][r]);
+        }
       }
     // ---- O^T += V^T . P^T : this tile's V pieces have landed (the next tile's 16 may fly)
-    if (NBUF == 2 && t + 4 < ntiles) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const char* vt_ = vbuf + buf * DEC_VTILE;
+    if (NBUF == 2 && t + 4 < ntiles) {
+      if (FP8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+    } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const char* vt_ = vbuf + buf * VT;
 #pragma unroll
     for (int sx = 0; sx < 2; ++sx) {
       const int key0 = sx * 32 + g * 4 + vq;
       const int key1 = key0 + 16;
+      if constexpr (FP8) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {   // 32 dims: lane fr of a group <- dims 32 c + 2 fr, + 1 of the keys key0 .. + 3 and key1 .. + 3
+          const int ch = 2 * c + (vp >> 1);
+          const int a0 = key0 * 128 + ((ch ^ (((key0 >> 1) & 3) << 1)) << 4) + (vp & 1) * 8;
+          const int a1 = key1 * 128 + ((ch ^ (((key1 >> 1) & 3) << 1)) << 4) + (vp & 1) * 8;
+          const u32x2 r0 = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(vt_ + a0)));
+          const u32x2 r1 = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(vt_ + a1)));
+          u32x4 ve, vo;   // even / odd dim of the pair, keys in operand order
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const u32x2 rr = h ? r1 : r0;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {   // dword j: (key 2j: even, odd, key 2j + 1: even, odd)
+              const f32x2 ka = __builtin_amdgcn_cvt_pk_f32_fp8((int)rr[j], false), kb = __builtin_amdgcn_cvt_pk_f32_fp8((int)rr[j], true);
+              ve[2 * h + j] = pack_bf16_hi(ka[0], kb[0]);
+              vo[2 * h + j] = pack_bf16_hi(ka[1], kb[1]);
+            }
+          }
+          o[2 * c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ve), pf[sx], o[2 * c], 0, 0, 0);
+          o[2 * c + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, vo), pf[sx], o[2 * c + 1], 0, 0, 0);
+        }
+        continue;
+      }
 #pragma unroll
       for (int d = 0; d < C::DT; ++d) {
         const int ch = 2 * d + (vp >> 1);
@@ -1326,6 +1480,24 @@ __global__ __launch_bounds__(256) void attn_decode_fused_kernel(
       Lt = __builtin_fmaf(mg[(size_t)k * 34 * 64 + 64 + l], f[k], Lt);
     }
     const float inv = 1.0f / Lt;
+    if constexpr (FP8) {   // accumulator 2 c + par, row 4 g + r is dim 32 c + 8 g + 2 r + par
+      bf16_t* op8 = O + (long)b * ldo + (long)(hk * G + fr) * 128 + g * 8;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        bf16x8 ov;
+#pragma unroll
+        for (int par = 0; par < 2; ++par)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            float acc = 0.f;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc = __builtin_fmaf(mg[(size_t)k * 34 * 64 + (2 + (2 * c + par) * 4 + r) * 64 + l], f[k], acc);
+            ov[2 * r + par] = f2bf(acc * inv);
+          }
+        *(bf16x8*)(op8 + c * 32) = ov;
+      }
+      return;
+    }
     bf16_t* op = O + (long)b * ldo + (long)(hk * G + fr) * 128 + g * 4;
 #pragma unroll
     for (int d = 0; d < C::DT; ++d) {
@@ -1380,8 +1552,31 @@ int owc_launch_attention(const void* Q, long q_ts, long q_hs, const void* K, lon
 // Fused decode step: rope(q, k) of the fed token + KV-cache write + attention (head_dim 128).  `O` rows are [B][n_q * 128].
 int owc_launch_attn_decode_fused(const void* qkv, long ld, const int* pos, const float* cos_t, const float* sin_t, void* kc,
                                  void* vc, const int* slot, const int* write_idx, const int* k_len, void* O, long ldo, int B,
-                                 int n_q, int n_kv, int s_max, float scale, hipStream_t st) {
+                                 int n_q, int n_kv, int s_max, float scale, hipStream_t st, int kv_fp8, float* k_scale,
+                                 float* v_scale) {
   if (B <= 0 || n_q <= 0 || n_kv <= 0 || (n_q % n_kv) || n_q / n_kv > 16 || (ld & 7) || (ldo & 3)) return OWC_ERR_SHAPE;
+  if (kv_fp8) {   // e4m3 cache: codes in kc / vc, one fp32 scale per cache row
+    if (!k_scale || !v_scale) return OWC_ERR_ARG;
+    if (ldo & 7) return OWC_ERR_SHAPE;   // 16-byte output stores
+    static bool attr8_set = false;
+    if (!attr8_set) {
+      if (hipFuncSetAttribute((const void*)attn_decode_fused_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * DEC_VTILE8) != hipSuccess ||
+          hipFuncSetAttribute((const void*)attn_decode_fused_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, DEC_MERGE) != hipSuccess)
+        return OWC_ERR_HIP;
+      attr8_set = true;
+    }
+    const int prof8 = owc_gemm_profile_begin(0.0, OWC_PROF_ATTN_DECODE, st);
+    if (B * n_kv > g_decode_nbuf1_min_blocks)
+      hipLaunchKernelGGL((attn_decode_fused_kernel<1, true>), dim3(B * n_kv), dim3(256), DEC_MERGE, st, (const bf16_t*)qkv, ld, pos, cos_t,
+                         sin_t, (bf16_t*)kc, (bf16_t*)vc, slot, write_idx, k_len, (bf16_t*)O, ldo, n_q, n_kv, s_max,
+                         scale * 1.4426950408889634f, k_scale, v_scale);
+    else
+      hipLaunchKernelGGL((attn_decode_fused_kernel<2, true>), dim3(B * n_kv), dim3(256), 8 * DEC_VTILE8, st, (const bf16_t*)qkv, ld, pos, cos_t,
+                         sin_t, (bf16_t*)kc, (bf16_t*)vc, slot, write_idx, k_len, (bf16_t*)O, ldo, n_q, n_kv, s_max,
+                         scale * 1.4426950408889634f, k_scale, v_scale);
+    owc_gemm_profile_end(prof8, st);
+    return hipGetLastError() == hipSuccess ? OWC_OK : OWC_ERR_HIP;
+  }
   static bool attr_set = false;
   if (!attr_set) {
     if (hipFuncSetAttribute((const void*)attn_decode_fused_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * DEC_VTILE) != hipSuccess ||
@@ -1395,11 +1590,11 @@ int owc_launch_attn_decode_fused(const void* qkv, long ld, const int* pos, const
   if (B * n_kv > g_decode_nbuf1_min_blocks)
     hipLaunchKernelGGL(attn_decode_fused_kernel<1>, dim3(B * n_kv), dim3(256), 4 * DEC_VTILE, st, (const bf16_t*)qkv, ld, pos, cos_t,
                        sin_t, (bf16_t*)kc, (bf16_t*)vc, slot, write_idx, k_len, (bf16_t*)O, ldo, n_q, n_kv, s_max,
-                       scale * 1.4426950408889634f);
+                       scale * 1.4426950408889634f, nullptr, nullptr);
   else
     hipLaunchKernelGGL(attn_decode_fused_kernel<2>, dim3(B * n_kv), dim3(256), 8 * DEC_VTILE, st, (const bf16_t*)qkv, ld, pos, cos_t,
                        sin_t, (bf16_t*)kc, (bf16_t*)vc, slot, write_idx, k_len, (bf16_t*)O, ldo, n_q, n_kv, s_max,
-                       scale * 1.4426950408889634f);
+                       scale * 1.4426950408889634f, nullptr, nullptr);
   owc_gemm_profile_end(prof, st);
   return hipGetLastError() == hipSuccess ? OWC_OK : OWC_ERR_HIP;
 }

@@ -180,6 +180,49 @@ __global__ __launch_bounds__(256) void vision_rope_kernel(bf16_t* __restrict__ q
   *(bf16x4*)(p + i0 + half) = ob;
 }
 
+// fp8 KV cache, prefill: the K / V rows a prefill launch wrote into the bf16 staging layer (mrope_kv_kernel's addressing) are
+// quantised into one layer of the e4m3 cache - per (token, kv head) row of 128 exactly what quant_rows_fp8_kernel computes
+// (scale = amax / 448, 1 for a zero row; codes RNE, saturating).  16 lanes per row, 8 values each; a shared-prefix row
+// (tok_slot < 0) is read from the first slot of the broadcast range and written to every slot of it.
+__global__ __launch_bounds__(256) void kv_quant_fp8_kernel(
+    const bf16_t* __restrict__ ks, const bf16_t* __restrict__ vs, uint8_t* __restrict__ k8, uint8_t* __restrict__ v8,
+    float* __restrict__ ksc, float* __restrict__ vsc, const int* __restrict__ tok_slot, const int* __restrict__ tok_idx, int T,
+    int n_kv, int s_max, int bcast_first, int bcast_n) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int c = idx & 15;
+  long r = idx >> 4;
+  const int is_v = r & 1;
+  r >>= 1;
+  const int kvh = r % n_kv;
+  const long t = r / n_kv;
+  if (t >= T) return;   // whole 16-lane groups leave together
+  const int s0 = tok_slot[t] < 0 ? bcast_first : tok_slot[t];
+  const int ns = tok_slot[t] < 0 ? bcast_n : 1;
+  const long src_row = ((long)s0 * n_kv + kvh) * s_max + tok_idx[t];
+  const bf16x8 x = *(const bf16x8*)((is_v ? vs : ks) + src_row * 128 + c * 8);
+  float amax = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(bf2f(x[e])));
+#pragma unroll
+  for (int o = 1; o <= 8; o <<= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+  const float scale = amax > 0.f ? amax / 448.0f : 1.0f;
+  float v[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) v[e] = fminf(fmaxf(bf2f(x[e]) / scale, -448.0f), 448.0f);
+  int lo = 0, hi = 0;
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], lo, false);
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], lo, true);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[4], v[5], hi, false);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[6], v[7], hi, true);
+  uint8_t* q = is_v ? v8 : k8;
+  float* sc = is_v ? vsc : ksc;
+  for (int sl = s0; sl < s0 + ns; ++sl) {
+    const long row = ((long)sl * n_kv + kvh) * s_max + tok_idx[t];
+    *(int2*)(q + row * 128 + c * 8) = make_int2(lo, hi);
+    if (c == 0) sc[row] = scale;
+  }
+}
+
 // Decoder M-RoPE (HF apply_multimodal_rotary_pos_emb :180-222) on the fused qkv buffer
 // [T, (H + 2 KV) * 128]: q rotated in place, rotated k and v written into the KV cache
 // cache[(slot*KV + kvh) * s_max + idx][128].  bf16 arithmetic with torch's rounding sequence:
@@ -1143,6 +1186,17 @@ int owc_launch_mrope_kv(void* qkv, long ld, const int* pos3, long pos_stride, co
   hipLaunchKernelGGL(mrope_kv_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
                      (bf16_t*)qkv, ld, pos3, pos_stride, cos_t, sin_t, (bf16_t*)kc, (bf16_t*)vc,
                      tok_slot, tok_idx, T, n_q, n_kv, s_max, sec0, sec1, bcast_first, bcast_n);
+  return hipGetLastError() == hipSuccess ? OWC_OK : OWC_ERR_HIP;
+}
+
+int owc_launch_kv_quant_fp8(const void* k_stage, const void* v_stage, void* k8, void* v8, float* k_scale, float* v_scale,
+                            const int* tok_slot, const int* tok_idx, int T, int n_kv, int s_max, int bcast_first, int bcast_n,
+                            hipStream_t st) {
+  if (T <= 0 || n_kv <= 0 || s_max <= 0) return OWC_ERR_SHAPE;
+  const long total = (long)T * n_kv * 2 * 16;
+  hipLaunchKernelGGL(kv_quant_fp8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const bf16_t*)k_stage,
+                     (const bf16_t*)v_stage, (uint8_t*)k8, (uint8_t*)v8, k_scale, v_scale, tok_slot, tok_idx, T, n_kv, s_max,
+                     bcast_first, bcast_n);
   return hipGetLastError() == hipSuccess ? OWC_OK : OWC_ERR_HIP;
 }
 

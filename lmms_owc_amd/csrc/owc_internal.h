@@ -131,7 +131,11 @@ void owc_llm_set_prune_last(int v);
 void owc_llm_set_decode_fuse(int v);
 int owc_launch_attn_decode_fused(const void* qkv, long ld, const int* pos, const float* cos_t, const float* sin_t, void* kc,
                                  void* vc, const int* slot, const int* write_idx, const int* k_len, void* O, long ldo, int B,
-                                 int n_q, int n_kv, int s_max, float scale, hipStream_t st);
+                                 int n_q, int n_kv, int s_max, float scale, hipStream_t st, int kv_fp8 = 0, float* k_scale = nullptr,
+                                 float* v_scale = nullptr);
+int owc_launch_kv_quant_fp8(const void* k_stage, const void* v_stage, void* k8, void* v8, float* k_scale, float* v_scale,
+                            const int* tok_slot, const int* tok_idx, int T, int n_kv, int s_max, int bcast_first, int bcast_n,
+                            hipStream_t st);
 int owc_launch_clip_patchify(const uint8_t* img, void* out, long ldo, int kpad, int n_img, int S,
                              const float* mean, const float* stdv, hipStream_t st);
 int owc_launch_clip_embed(const void* pe, const void* pos_cls, void* x, int n_img, int tokens, int E,

@@ -165,6 +165,17 @@ size_t owc_llm_workspace_bytes(const owc_llm_weights* w, int T, int n_seq) {
   return b + 1024;
 }
 
+// an fp8 KV cache is read by the fused decode attention only (head_dim 128, <= 16 q heads per kv head) and needs its scale and
+// staging buffers
+static const char* kv_cache_error(const owc_llm_weights* w, const owc_kv_cache* cache, bool prefill) {
+  if (cache->dtype == OWC_KV_BF16) return nullptr;
+  if (cache->dtype != OWC_KV_FP8) return "owc_kv_cache.dtype must be OWC_KV_BF16 or OWC_KV_FP8";
+  if (w->head_dim != 128 || w->n_q_heads / w->n_kv_heads > 16) return "an fp8 KV cache needs head_dim 128 and at most 16 q heads per kv head";
+  if (!cache->k_scale || !cache->v_scale) return "an fp8 KV cache needs k_scale and v_scale";
+  if (prefill && (!cache->k_stage || !cache->v_stage)) return "prefill into an fp8 KV cache needs k_stage and v_stage";
+  return nullptr;
+}
+
 static int g_decode_fuse = 1;  // owc_tuning_set("decode_fuse", 0): decode steps run mrope_kv_kernel + the generic attention kernel (A-B / parity)
 static int g_prune_last = 1;  // owc_tuning_set("prefill_prune_last", 0): full last layer (the A side of the bit-identity test)
 
@@ -183,8 +194,10 @@ static int llm_layers(owc_ctx* ctx, const owc_llm_weights* w, const owc_kv_cache
   const int NQKV = (Hq + 2 * Hkv) * hd;
   const int G = Hq / Hkv;
   const float scale = 1.0f / sqrtf((float)hd);
-  const size_t layer_elems = (size_t)cache->n_slots * Hkv * cache->s_max * hd;
+  const size_t layer_rows = (size_t)cache->n_slots * Hkv * cache->s_max;
+  const size_t layer_elems = layer_rows * hd;
   const bool fp8 = w->weight_dtype == OWC_WEIGHTS_FP8;
+  const bool kv8 = cache->dtype == OWC_KV_FP8;   // e4m3 codes + row scales; prefill works in the bf16 staging layer
   // one decoder projection over M rows: bf16 weights -> owc_gemm_bf16; fp8 weights -> per-token quantisation of the input
   // rows, then the scaled-fp8-MFMA GEMM with the same fused epilogue
   // (`in` == NULL: the rows are already in q8 / qs, put there by the fused RMSNorm + quantise kernel)
@@ -200,8 +213,15 @@ static int llm_layers(owc_ctx* ctx, const owc_llm_weights* w, const owc_kv_cache
   };
   for (int i = 0; i < w->n_layers; ++i) {
     const owc_llm_layer& L = w->layers[i];
-    bf16_t* kc = (bf16_t*)cache->k + (size_t)i * layer_elems;
-    bf16_t* vc = (bf16_t*)cache->v + (size_t)i * layer_elems;
+    void* kc = (char*)cache->k + (size_t)i * layer_elems * (kv8 ? 1 : 2);
+    void* vc = (char*)cache->v + (size_t)i * layer_elems * (kv8 ? 1 : 2);
+    float* ksc = kv8 ? cache->k_scale + (size_t)i * layer_rows : nullptr;
+    float* vsc = kv8 ? cache->v_scale + (size_t)i * layer_rows : nullptr;
+    void *k8 = kc, *v8 = vc;
+    if (kv8 && !decode) {   // prefill attention reads what this launch wrote, in bf16 (include/owc.h: owc_kv_cache)
+      kc = cache->k_stage;
+      vc = cache->v_stage;
+    }
     const bool tail = last_index && g_prune_last && i == w->n_layers - 1;  // last prefill layer: only the n_out last-token rows go on
     // self-attention block (HF:601-614); a handful of rows (decode at the reference's batch size): the projection normalises its own
     // activations (gemm_bf16_skinny_norm_kernel) - same bits as the two launches, one launch less
@@ -217,6 +237,8 @@ static int llm_layers(owc_ctx* ctx, const owc_llm_weights* w, const owc_kv_cache
     if (!fused_decode)
       OWC_TRY(owc_launch_mrope_kv(qkv, NQKV, pos3, pos_stride, w->rope_cos, w->rope_sin, kc, vc, tok_slot,
                                   tok_idx, T, Hq, Hkv, cache->s_max, w->mrope_sec0, w->mrope_sec1, bcast_first, bcast_n, st));
+    if (kv8 && !decode)
+      OWC_TRY(owc_launch_kv_quant_fp8(kc, vc, k8, v8, ksc, vsc, tok_slot, tok_idx, T, Hkv, cache->s_max, bcast_first, bcast_n, st));
     int M = T;
     void* xr = x;
     if (tail) {
@@ -239,7 +261,7 @@ static int llm_layers(owc_ctx* ctx, const owc_llm_weights* w, const owc_kv_cache
     } else if (fused_decode) {
       // rope of the fed token + KV-cache write + attention over the cache in one launch (attention.hip, round 3)
       OWC_TRY(owc_launch_attn_decode_fused(qkv, NQKV, pos3, w->rope_cos, w->rope_sin, kc, vc, tok_slot, tok_idx, k_len, attn,
-                                           (long)Hq * hd, T, Hq, Hkv, cache->s_max, scale, st));
+                                           (long)Hq * hd, T, Hq, Hkv, cache->s_max, scale, st, kv8, ksc, vsc));
     } else {
       // one query row per q head: map the G heads of a kv group onto the "rows" of the kernel
       OWC_TRY(owc_launch_attention(qkv, hd, (long)G * hd, kc, hd, (long)cache->s_max * hd, vc, hd,
@@ -279,6 +301,7 @@ int owc_llm_prefill(owc_ctx* ctx, const owc_llm_weights* w, const owc_kv_cache* 
   const bool scoring = score_mode == OWC_PREFILL_SCORE_ROWS;
   const int n_rows = scoring ? n_out : n_seq;
   if (w->head_dim != 128) OWC_FAIL(ctx, OWC_ERR_SHAPE, "owc_llm_prefill: head_dim must be 128");
+  if (const char* e = kv_cache_error(w, cache, true)) OWC_FAIL(ctx, OWC_ERR_SHAPE, e);
   if (w->weight_dtype == OWC_WEIGHTS_FP8 && ((w->d_model % 128) || (w->d_ff % 128)))
     OWC_FAIL(ctx, OWC_ERR_SHAPE, "owc_llm_prefill: fp8 weights need d_model and d_ff to be multiples of 128");
   if (ws_bytes < owc_llm_workspace_bytes(w, T, n_rows)) OWC_FAIL(ctx, OWC_ERR_WORKSPACE, "owc_llm_prefill: workspace too small");
@@ -348,6 +371,9 @@ int owc_llm_decode_step(owc_ctx* ctx, const owc_llm_weights* w, const owc_kv_cac
       !q_start || !o_start || !q_len || !done || !out_tokens || !workspace)
     return OWC_ERR_ARG;
   if (ws_bytes < owc_llm_workspace_bytes(w, B, B)) OWC_FAIL(ctx, OWC_ERR_WORKSPACE, "owc_llm_decode_step: workspace too small");
+  if (const char* e = kv_cache_error(w, cache, false)) OWC_FAIL(ctx, OWC_ERR_SHAPE, e);
+  if (cache->dtype == OWC_KV_FP8 && !g_decode_fuse)
+    OWC_FAIL(ctx, OWC_ERR_SHAPE, "owc_llm_decode_step: an fp8 KV cache needs the fused decode attention (decode_fuse = 0 is set)");
   hipStream_t st = (hipStream_t)stream;
   const int d = w->d_model;
   Carver cv(workspace, ws_bytes);

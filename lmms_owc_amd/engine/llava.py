@@ -16,7 +16,7 @@ import torch
 
 from .. import _lib
 from . import anyres
-from .qwen2vl import BF16, F32, Qwen2VLEngine, Qwen2VLWeights
+from .qwen2vl import BF16, F32, Qwen2VLEngine, Qwen2VLWeights, check_kv_dtype
 
 CLIP_PATCH = 14
 
@@ -48,8 +48,12 @@ class LlavaDims:
     max_positions: int = 4096
     merge: int = 1
     decoder_dtype: str = "bf16"        # "fp8": see Qwen2VLDims.decoder_dtype
+    kv_dtype: str = "bf16"             # "fp8": see Qwen2VLDims.kv_dtype
     # LLaVA-NeXT anyres (None -> LLaVA-1.5: one 336x336 view)
     grid_pinpoints: tuple | None = None
+
+    def __post_init__(self):
+        check_kv_dtype(self)
 
     @property
     def grid(self) -> int:

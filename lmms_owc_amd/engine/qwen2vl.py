@@ -23,6 +23,22 @@ from . import positions
 BF16, F32, I32 = torch.bfloat16, torch.float32, torch.int32
 
 
+def check_kv_dtype(d) -> None:
+    """`kv_dtype` of a dims object: "bf16" or "fp8"; the fp8 cache is read by the fused decode attention only (include/owc.h)."""
+    if d.kv_dtype not in ("bf16", "fp8"):
+        raise ValueError("kv_dtype must be 'bf16' or 'fp8'")
+    if d.kv_dtype == "fp8" and (d.head_dim != 128 or d.n_q_heads // d.n_kv_heads > 16):
+        raise ValueError("kv_dtype='fp8' needs head_dim 128 and at most 16 query heads per kv head (the fused decode attention)")
+
+
+def kv_bytes_per_token(d) -> int:
+    """Bytes of KV cache one cached token of one sequence costs (all layers, K and V).  fp8: codes + an fp32 scale per (kv head) row,
+    plus the token's share of the one-layer bf16 staging buffer of the prefill."""
+    if getattr(d, "kv_dtype", "bf16") == "fp8":
+        return d.n_layers * 2 * d.n_kv_heads * (d.head_dim + 4) + 2 * d.n_kv_heads * d.head_dim * 2
+    return d.n_layers * 2 * d.n_kv_heads * d.head_dim * 2
+
+
 @dataclass
 class Qwen2VLDims:
     # vision tower
@@ -49,11 +65,15 @@ class Qwen2VLDims:
     max_grid: int = 1024           # vision rope table length (patches per side): covers max_pixels = 1024 * 28 * 28 at the
                                    # processor's 200:1 aspect limit (sqrt(802816 * 200) / 14 = 905); checked per launch
     decoder_dtype: str = "bf16"    # "fp8": decoder projections as e4m3fn weights + per-token e4m3fn activations (config #5)
+    kv_dtype: str = "bf16"         # "fp8": KV cache as e4m3fn codes + one fp32 scale per (token, kv head) row
     # vision tower variant: 0 = Qwen2-VL (LayerNorm, fc1 -> quick_gelu -> fc2), 1 = Qwen2.5-VL (RMSNorm, gated SiLU MLP with
     # biases - `v_mlp` is its intermediate size, 3420 -, window attention except in the `v_fullatt` blocks)
     v_variant: int = 0
     v_window: int = 112
     v_fullatt: tuple = ()
+
+    def __post_init__(self):
+        check_kv_dtype(self)
 
 
 DIMS = {
@@ -341,6 +361,8 @@ class Qwen2VLEngine:
         self.prefill_chunk_tokens = prefill_chunk_tokens
         self._ws: torch.Tensor | None = None
         self._kv: tuple | None = None      # the engine's grow-only K / V cache pair (reserve_kv)
+        self._kv_aux: tuple | None = None  # kv_dtype="fp8": (k_scale, v_scale, k_stage, v_stage), sized with the pair
+        check_kv_dtype(self.d)
         self._lib = _lib.load()
         self._ctx = _lib.ctx(self.dev_index)
         # HF's repetition penalty for every generation of this engine (1.0 = off): a model plug-in sets it from the checkpoint's
@@ -359,6 +381,8 @@ class Qwen2VLEngine:
 
     def reserve_kv(self, elems: int) -> tuple[torch.Tensor, torch.Tensor]:
         """The engine's K and V cache blocks (bf16, `elems` each): ONE grow-only pair per engine, handed out as views.
+        kv_dtype="fp8": the pair holds e4m3fn codes (uint8) and the engine keeps, sized with it, the fp32 row scales
+        (elems / head_dim each) and the one-layer bf16 staging pair of the prefill (elems / n_layers each): `_kv_aux`.
         Passes of a task differ in size (the adaptive ramp of `generate_until`, carried sequences, generation lengths); a fresh
         `torch.empty` per pass made every new size a fresh hipMalloc beside the cached blocks of the earlier sizes - seconds per
         pass once the blocks are tens of GB, and out-of-memory retries for an MHA decoder (LLaVA-1.5: 0.5 MB of KV per token).
@@ -366,22 +390,49 @@ class Qwen2VLEngine:
         old pair goes back to the driver first (`empty_cache`), so the peak is the new pair, not the sum."""
         kv = self._kv
         if kv is None or kv[0].numel() < elems:
-            self._kv = kv = None
+            self._kv = kv = self._kv_aux = None
             if elems * 2 > (1 << 30):
                 torch.cuda.empty_cache()
-            self._kv = kv = (torch.empty(int(elems), dtype=BF16, device=self.device), torch.empty(int(elems), dtype=BF16, device=self.device))
+            fp8 = self.d.kv_dtype == "fp8"
+            new = lambda n, dt: torch.empty(int(n), dtype=dt, device=self.device)
+            self._kv = kv = (new(elems, torch.uint8 if fp8 else BF16), new(elems, torch.uint8 if fp8 else BF16))
+            if fp8:
+                rows, stage = elems // self.d.head_dim, -(-elems // self.d.n_layers)
+                self._kv_aux = (new(rows, F32), new(rows, F32), new(stage, BF16), new(stage, BF16))
         return kv[0][:elems], kv[1][:elems]
+
+    def _kv_cache(self, kc: torch.Tensor, vc: torch.Tensor, n_slots: int, s_max: int) -> _lib.KvCache:
+        """owc_kv_cache over views of the engine's pair (`reserve_kv`); fp8: with the scales and the staging layer."""
+        if self.d.kv_dtype != "fp8":
+            return _lib.KvCache(kc.data_ptr(), vc.data_ptr(), n_slots, s_max)
+        ks, vs, kst, vst = self._kv_aux
+        return _lib.KvCache(kc.data_ptr(), vc.data_ptr(), n_slots, s_max, _lib.KV_FP8, ks.data_ptr(), vs.data_ptr(), kst.data_ptr(), vst.data_ptr())
+
+    def _kv_views(self, kc: torch.Tensor, vc: torch.Tensor, n_slots: int, s_max: int) -> list[torch.Tensor]:
+        """Everything a sequence's cache rows consist of, as [n_layers, n_slots, n_kv_heads, s_max, ...] views: K, V (+ their row
+        scales for an fp8 cache) - what a hand-over between passes copies."""
+        d = self.d
+        out = [kc.view(d.n_layers, n_slots, d.n_kv_heads, s_max, d.head_dim), vc.view(d.n_layers, n_slots, d.n_kv_heads, s_max, d.head_dim)]
+        if d.kv_dtype == "fp8":
+            rows = d.n_layers * n_slots * d.n_kv_heads * s_max
+            out += [t[:rows].view(d.n_layers, n_slots, d.n_kv_heads, s_max) for t in self._kv_aux[:2]]
+        return out
+
+    def kv_bytes(self, n_slots: int, s_max: int) -> int:
+        """Device bytes of the KV cache of `n_slots` sequences of `s_max` rows (fp8: codes, scales and the staging layer)."""
+        return kv_bytes_per_token(self.d) * int(n_slots) * int(s_max)
 
     def held_bytes(self) -> int:
         """Device bytes this engine keeps between passes and reuses (the K / V pair and the workspace): memory a batch-size decision
         must count as FREE, or the batch of a later task would depend on what an earlier one left allocated (`engine_batch`)."""
         kv = 2 * self._kv[0].numel() * self._kv[0].element_size() if self._kv is not None else 0
+        kv += sum(t.numel() * t.element_size() for t in self._kv_aux) if self._kv_aux is not None else 0
         return kv + (self._ws.numel() if self._ws is not None else 0)
 
     def release_kv(self) -> None:
         """Hand the K / V pair (tens of GB after a large pass) back: for a caller that is done generating and needs the memory for
         something else (another model on the same GPU).  The next pass simply reserves a new pair."""
-        self._kv = None
+        self._kv = self._kv_aux = None
 
     # -- vision tower ------------------------------------------------------------------
     def encode_images(self, pixel_values: torch.Tensor, grid_thw) -> torch.Tensor:
@@ -521,11 +572,11 @@ class Qwen2VLEngine:
             s_max = (max(s_max, int(lens.max()) + max_new_tokens + 2) + 15) // 16 * 16
         cache_elems = d.n_layers * n_slots * Hkv * s_max * d.head_dim
         kc, vc = self.reserve_kv(cache_elems)
-        cache = _lib.KvCache(kc.data_ptr(), vc.data_ptr(), n_slots, s_max)
-        if NC:   # the carried sequences' K / V rows move into slots B.. of this pass's cache (one strided copy each)
+        cache = self._kv_cache(kc, vc, n_slots, s_max)
+        if NC:   # the carried sequences' K / V rows (fp8: codes and scales) move into slots B.. of this pass's cache (one strided copy each)
             w_c = cin["k"].shape[3]
-            kc.view(d.n_layers, n_slots, Hkv, s_max, d.head_dim)[:, B:Bx, :, :w_c].copy_(cin["k"])
-            vc.view(d.n_layers, n_slots, Hkv, s_max, d.head_dim)[:, B:Bx, :, :w_c].copy_(cin["v"])
+            for dst, src in zip(self._kv_views(kc, vc, n_slots, s_max), [cin["k"], cin["v"]] + list(cin.get("kv_scales") or [])):
+                dst[:, B:Bx, :, :w_c].copy_(src)
 
         # positions (host integer bookkeeping)
         pos_list, max_pos, img_index = self._positions_and_image_rows(prompts, grids_per_prompt, img_embeds, img_rows)
@@ -768,6 +819,8 @@ class Qwen2VLEngine:
 
         d = self.d
         B, k = len(prompts), int(num_beams)
+        if d.kv_dtype == "fp8":
+            raise ValueError("beam search on an fp8 KV cache is not supported (kv_dtype='fp8' with num_beams > 1)")
         if k < 2:
             raise ValueError("generate_beam is for num_beams >= 2 (one beam is `generate`)")
         rep = float(self.repetition_penalty if repetition_penalty is None else repetition_penalty)
@@ -929,9 +982,8 @@ class Qwen2VLEngine:
         cached = st[2, comp].astype(np.int64)                       # tokens in its cache = the next write index
         w_c = int(cached.max())
         sel = torch.from_numpy(idx.astype(np.int64)).to(self.device)
-        kv = (kc.view(d.n_layers, n_slots, d.n_kv_heads, s_max, d.head_dim), vc.view(d.n_layers, n_slots, d.n_kv_heads, s_max, d.head_dim))
-        k_out = kv[0][:, :, :, :w_c].index_select(1, sel)
-        v_out = kv[1][:, :, :, :w_c].index_select(1, sel)
+        kv = [t[:, :, :, :w_c].index_select(1, sel) for t in self._kv_views(kc, vc, n_slots, s_max)]   # fp8: codes, then the row scales
+        k_out, v_out = kv[0], kv[1]
         tokens, tags, forced_rest = [], [], []
         for r in idx:
             r = int(r)
@@ -948,7 +1000,8 @@ class Qwen2VLEngine:
             forced_rest.append(fr)
         carry["out"] = {"k": k_out, "v": v_out, "cached": cached, "tok": st[0, comp].astype(np.int64), "pos": st[1, comp].astype(np.int64),
                         "emitted": emitted[idx], "remaining": (cap - emitted)[idx], "tokens": tokens, "tags": tags,
-                        "forced_rest": forced_rest, "stream": None if stream_of is None else np.asarray(stream_of)[idx]}
+                        "forced_rest": forced_rest, "stream": None if stream_of is None else np.asarray(stream_of)[idx],
+                        "kv_scales": kv[2:]}
 
     def score(self, ids, img_embeds: torch.Tensor | None, grids: list, start: int, *, img_rows=None):
         """Teacher-forced scoring of ONE token sequence (prompt + continuation) in a single prefill: the logits of the positions

@@ -176,6 +176,8 @@ class PassPipeline:
         """Before a task's first pass: grow the engine's K / V pair ONCE to what a full pass of this task needs (the ramp's passes
         are views of it), instead of once per pass size of the ramp.  Prompt lengths are those of the first prepared unit plus a
         tenth (requests are collated longest-first); a longer prompt later simply grows the pair again."""
+        from ..engine.qwen2vl import kv_bytes_per_token
+
         d, eng = self._dims, self._model
         if not hasattr(eng, "reserve_kv"):
             return
@@ -185,9 +187,9 @@ class PassPipeline:
             # slots for sequences handed over between passes: as many as a pass has, if 40 % of the memory left beside one pass's
             # cache holds them twice (a carried sequence's rows exist in the export AND in the next pass's cache for a moment);
             # none - no hand-over in this task - when not even 64 fit (an MHA decoder at a batch that fills the memory)
-            slot_bytes = 4 * d.n_layers * d.n_kv_heads * d.head_dim * rows                    # K and V, bf16
+            slot_bytes = kv_bytes_per_token(d) * rows                                         # K and V, by kv_dtype
             free = torch.cuda.mem_get_info(self._device)[0] + torch.cuda.memory_reserved(self._device) - torch.cuda.memory_allocated(self._device)
-            held = 4 * eng._kv[0].numel() if getattr(eng, "_kv", None) else 0                 # (the current pair is released when it grows)
+            held = eng.kv_bytes(1, eng._kv[0].numel() // (d.n_layers * d.n_kv_heads * d.head_dim)) if getattr(eng, "_kv", None) else 0   # (the current pair is released when it grows)
             fit = int(0.4 * (free + held - slots * slot_bytes) / (2 * slot_bytes))
             self._carry_capacity = max(0, min((slots + 63) // 64 * 64, fit // 64 * 64))
             slots = slots + self._carry_capacity
@@ -339,7 +341,7 @@ class PassPipeline:
         reordered = utils.Collator([reg.args for reg in requests], _collate, grouping=True)
         max_new = max([int(r.args[1].get("max_new_tokens", default_max_new)) for r in requests] + [1])
         eb = self.engine_batch(max_new)
-        beams = max([beams_from_gen_kwargs(r.args[1]) for r in requests] + [1])
+        beams = max([beams_from_gen_kwargs(r.args[1], self._dims) for r in requests] + [1])
         if beams > 1:   # a beam-search pass holds num_beams hypotheses (cache slots, decode rows) per request
             eb = max(self.batch_size, eb // beams)
         unit = eb if eb < 256 else max(64, eb // 16)
@@ -660,13 +662,16 @@ def pass_key(max_new: int, sampling: dict | None, num_beams: int = 1) -> tuple:
     return (int(max_new), smp) if num_beams == 1 else (int(max_new), smp, int(num_beams))
 
 
-def beams_from_gen_kwargs(gen_kwargs: dict) -> int:
+def beams_from_gen_kwargs(gen_kwargs: dict, dims=None) -> int:
     """`num_beams` of a request (reference src/models/_qwen2_vl.py:308-329, _llava_hf.py:355-376: default 1, handed to HF's generate).
     Beams run under the engine's `repetition_penalty` (the checkpoint's generation_config.json value, which HF merges into the same
     call), applied to the log-probabilities as HF's beam search does: `Qwen2VLEngine.generate_beam`."""
     k = int(gen_kwargs.get("num_beams", 1) or 1)
     if k < 1:
         raise ValueError("num_beams must be >= 1")
+    if k > 1 and getattr(dims, "kv_dtype", "bf16") == "fp8":   # refused while the requests are parsed, before any engine pass runs
+        raise ValueError("num_beams > 1 is not supported with kv_dtype=fp8: beam search copies KV rows between hypotheses and has no "
+                         "fp8-cache form; run beam-search tasks with kv_dtype=bf16")
     if k > 32:   # owc_beam_candidates returns at most 64 = 2 x num_beams candidates per row: refuse here, not inside the first decode step
         raise ValueError("num_beams > 32 is not supported by the HIP decoder (owc_beam_candidates: k = 2 * num_beams <= 64)")
     return k

@@ -20,6 +20,7 @@ import torch
 
 from .. import _lib, utils
 from ..engine.llava import DIMS, NEXT_PINPOINTS, LlavaDims, LlavaEngine, LlavaWeights
+from ..engine.qwen2vl import kv_bytes_per_token
 from . import imageproc
 from ._api import register_model
 from ._base import Model, PassPipeline, beams_from_gen_kwargs, pass_key, sampling_from_gen_kwargs
@@ -71,11 +72,15 @@ class LLaVA(PassPipeline, Model):
     def __init__(self, model_name_or_path: str = "llava-hf/llava-1.5-7b-hf", attn_implementation: str | None = None,
                  chat_template: str | None = None, use_cache: bool = True, batch_size: int = 1, device_map: str = "auto",
                  dtype: str | torch.dtype = "bfloat16", load_in_8bit: bool = False, load_in_4bit: bool = False,
-                 decoder_dtype: str = "bf16", engine_batch: int | str = "auto", **kwargs) -> None:
+                 decoder_dtype: str = "bf16", kv_dtype: str = "bf16", engine_batch: int | str = "auto", **kwargs) -> None:
         # two kwargs beyond the reference's: fp8 decoder projections and `engine_batch` - `batch_size` is a
         # lower bound, tokens are batch-invariant (see Qwen2VL.__init__): "auto" = what fits in HBM (<= 512), n = exactly n, 0 = off
+        # `kv_dtype`: "fp8" = e4m3fn KV cache, see Qwen2VL.__init__
         if decoder_dtype not in ("bf16", "fp8"):
             raise ValueError("decoder_dtype must be 'bf16' or 'fp8'")
+        if kv_dtype not in ("bf16", "fp8"):
+            raise ValueError("kv_dtype must be 'bf16' or 'fp8'")
+        self._kv_dtype = kv_dtype
         if engine_batch != "auto" and (not isinstance(engine_batch, int) or engine_batch < 0):
             raise ValueError("engine_batch must be 'auto' or an integer >= 0")
         self._engine_batch_arg = engine_batch
@@ -93,7 +98,7 @@ class LLaVA(PassPipeline, Model):
         if name.startswith("synthetic:"):
             tok = LlavaByteTokenizer()
             dims = LlavaDims(**{**DIMS[name.split(":", 1)[1]].__dict__, "image_token_id": tok.image_token_id,
-                                "decoder_dtype": self._decoder_dtype})
+                                "decoder_dtype": self._decoder_dtype, "kv_dtype": self._kv_dtype})
             weights = LlavaWeights.random(dims, self._device, seed=1234)
             self._tokenizer = tok
         else:
@@ -103,7 +108,7 @@ class LLaVA(PassPipeline, Model):
 
                 path = Path(snapshot_download(name))
             dims = dims_from_hf_config(json.loads((path / "config.json").read_text()))
-            dims = LlavaDims(**{**dims.__dict__, "decoder_dtype": self._decoder_dtype})
+            dims = LlavaDims(**{**dims.__dict__, "decoder_dtype": self._decoder_dtype, "kv_dtype": self._kv_dtype})
             weights = LlavaWeights.from_state_dict(dims, LlavaCheckpoint(path), self._device)
             from transformers import AutoTokenizer
 
@@ -125,7 +130,7 @@ class LLaVA(PassPipeline, Model):
         d = self._dims
         views = 5 if d.grid_pinpoints else 1
         tokens = views * d.tokens + 128 + int(max_new_tokens)
-        per_req = (d.n_layers * 2 * d.n_kv_heads * d.head_dim * 2) * tokens + views * d.tokens * (d.d_model * 2 + d.v_embed * 24)
+        per_req = kv_bytes_per_token(d) * tokens + views * d.tokens * (d.d_model * 2 + d.v_embed * 24)
         cache = self.__dict__.setdefault("_auto_batch", {})   # once per max_new_tokens (see Qwen2VL.engine_batch)
         if max_new_tokens not in cache:
             free, _ = torch.cuda.mem_get_info(self._device)
@@ -217,7 +222,7 @@ class LLaVA(PassPipeline, Model):
                     break
                 smp = None if sampling is None else {**sampling, "stream_ids": [int(doc_ids[i]) * 64 + round_idx for i in active]}
                 rows = self._generate_chunk([contexts[i] for i in active], [visuals_per_doc[i] for i in active], max_new, feature_cache,
-                                            sampling=smp, num_beams=beams_from_gen_kwargs(gen_kwargs))
+                                            sampling=smp, num_beams=beams_from_gen_kwargs(gen_kwargs, self._dims))
                 for i, ans in zip(active, self.decode_tokens(rows)):
                     results[i].append(ans)
                 round_idx += 1
@@ -374,7 +379,7 @@ class LLaVA(PassPipeline, Model):
             dst, offs = buf.numpy(), np.cumsum([0] + [v.shape[0] for v in views])
             list(self._pool.map(lambda k: np.copyto(dst[offs[k]:offs[k + 1]], views[k]), range(len(views))))
             groups.append(buf)
-        num_beams = beams_from_gen_kwargs(gen_kwargs)
+        num_beams = beams_from_gen_kwargs(gen_kwargs, self._dims)
         key = pass_key(max_new, sampling, num_beams)
         return {"prompts": prompts, "images_per_prompt": images_per_prompt, "views_per_image": [v.shape[0] for v in views], "sizes": sizes,
                 "groups": groups, "max_new": max_new, "n": len(chunk), "sampling": sampling, "doc_ids": [int(x) for x in doc_ids], "key": key, "num_beams": num_beams}

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .. import _lib, ops, utils
-from ..engine.qwen2vl import DIMS, Qwen2VLDims, Qwen2VLEngine, Qwen2VLWeights
+from ..engine.qwen2vl import DIMS, Qwen2VLDims, Qwen2VLEngine, Qwen2VLWeights, kv_bytes_per_token
 from . import imageproc
 from ._api import register_model
 from ._base import Model, PassPipeline, beams_from_gen_kwargs, pass_key, sampling_from_gen_kwargs
@@ -63,7 +63,7 @@ class Qwen2VL(PassPipeline, Model):
                  use_flash_attention_2: bool | None = False, max_pixels: int = 1024 * 28 * 28,
                  min_pixels: int = 4 * 28 * 28, batch_size: int = 1, device_map: str = "auto",
                  dtype: str | torch.dtype = "bfloat16", load_in_8bit: bool = False, load_in_4bit: bool = False,
-                 decoder_dtype: str = "bf16", engine_batch: int | str = "auto", **kwargs) -> None:
+                 decoder_dtype: str = "bf16", kv_dtype: str = "bf16", engine_batch: int | str = "auto", **kwargs) -> None:
         # Two kwargs the reference does not have.  `decoder_dtype`: "fp8" runs the decoder projections on the e4m3fn path
         # (`--model_args decoder_dtype=fp8`).  `engine_batch`: how many requests one pass through the
         # engine takes.  The reference's scripts hard-code `--batch_size 1` (scripts/schedule_batch.sh:86, its wrapper supports
@@ -71,8 +71,13 @@ class Qwen2VL(PassPipeline, Model):
         # `batch_size` is only a LOWER bound: "auto" (default) raises it to what fits in HBM, at most 2048 (10.7 images/s at
         # batch 1, 138 at 64, 240 at 2048 for the 7B model); an integer fixes it; 0 keeps exactly `batch_size`.
         # The reference's bitsandbytes switches stay rejected.
+        # `kv_dtype`: "fp8" keeps the KV cache as e4m3fn codes + per-row scales (`--model_args kv_dtype=fp8`; combines with
+        # decoder_dtype=fp8; greedy / sampled generation only: num_beams > 1 is refused when the requests are parsed).
         if decoder_dtype not in ("bf16", "fp8"):
             raise ValueError("decoder_dtype must be 'bf16' or 'fp8'")
+        if kv_dtype not in ("bf16", "fp8"):
+            raise ValueError("kv_dtype must be 'bf16' or 'fp8'")
+        self._kv_dtype = kv_dtype
         if engine_batch != "auto" and (not isinstance(engine_batch, int) or engine_batch < 0):
             raise ValueError("engine_batch must be 'auto' or an integer >= 0")
         self._engine_batch_arg = engine_batch
@@ -93,6 +98,7 @@ class Qwen2VL(PassPipeline, Model):
         self._engine_batch_arg = 0
         self._model_name_or_path = "engine"
         self._decoder_dtype = engine.d.decoder_dtype
+        self._kv_dtype = getattr(engine.d, "kv_dtype", "bf16")
         self._max_pixels, self._min_pixels = 1024 * 28 * 28, 4 * 28 * 28
         self._device = engine.device
         self._rank, self._world_size = 0, 1
@@ -126,7 +132,7 @@ class Qwen2VL(PassPipeline, Model):
             return max(self.batch_size, int(arg))
         d = self._dims
         tokens = self._max_pixels // 784 + 64 + int(max_new_tokens)
-        per_req = (d.n_layers * 2 * d.n_kv_heads * d.head_dim * 2) * tokens + (self._max_pixels // 196) * 1176 * 2 \
+        per_req = kv_bytes_per_token(d) * tokens + (self._max_pixels // 196) * 1176 * 2 \
             + (self._max_pixels // 784) * d.d_model * 2
         # computed ONCE per max_new_tokens: after the first task torch's caching allocator holds the KV cache and workspaces,
         # `mem_get_info` would report them as used and later tasks would get a smaller batch, new chunk sizes and new allocations.
@@ -146,7 +152,8 @@ class Qwen2VL(PassPipeline, Model):
             key = name.split(":", 1)[1]
             dims = DIMS[key]
             tok = ByteTokenizer()
-            dims = Qwen2VLDims(**{**dims.__dict__, "image_token_id": tok.image_pad, "decoder_dtype": self._decoder_dtype})
+            dims = Qwen2VLDims(**{**dims.__dict__, "image_token_id": tok.image_pad, "decoder_dtype": self._decoder_dtype,
+                                  "kv_dtype": self._kv_dtype})
             weights = Qwen2VLWeights.random(dims, self._device, seed=1234)
             self._tokenizer = tok
         else:
@@ -156,7 +163,7 @@ class Qwen2VL(PassPipeline, Model):
 
                 path = Path(snapshot_download(name))
             dims = dims_from_hf_config(json.loads((path / "config.json").read_text()))
-            dims = Qwen2VLDims(**{**dims.__dict__, "decoder_dtype": self._decoder_dtype})
+            dims = Qwen2VLDims(**{**dims.__dict__, "decoder_dtype": self._decoder_dtype, "kv_dtype": self._kv_dtype})
             weights = Qwen2VLWeights.from_state_dict(dims, LazyCheckpoint(path), self._device)
             from transformers import AutoTokenizer
 
@@ -210,7 +217,7 @@ class Qwen2VL(PassPipeline, Model):
                 raise ValueError(f"Expected `gen_kwargs['until']` to be of type Union[str,list] but got {type(until)}")
             max_new = int(gen_kwargs.get("max_new_tokens", 128))
             sampling = sampling_from_gen_kwargs(gen_kwargs, getattr(self, "_default_top_k", 50))
-            num_beams = beams_from_gen_kwargs(gen_kwargs)
+            num_beams = beams_from_gen_kwargs(gen_kwargs, self._dims)
             docs = [self.task_dict[task][split][did] for did in doc_ids]
             # round 0: the reference flattens the batch's visuals and hands message i the i-th entry (:409-413, :482-483) - at its
             # batch size of one that is the document's FIRST image; later rounds get the list the task returns, whole
@@ -432,7 +439,7 @@ class Qwen2VL(PassPipeline, Model):
             groups.append(buf)
             i = j
         list(self._pool.map(lambda c: np.copyto(*c), copies))
-        num_beams = beams_from_gen_kwargs(gen_kwargs)
+        num_beams = beams_from_gen_kwargs(gen_kwargs, self._dims)
         key = pass_key(max_new, sampling, num_beams)
         return {"prompts": prompts, "grids": grids_per_prompt, "groups": groups, "max_new": max_new, "n": len(chunk),
                 "sampling": sampling, "doc_ids": [int(d) for d in doc_ids], "key": key, "num_beams": num_beams}

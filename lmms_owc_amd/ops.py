@@ -143,15 +143,32 @@ def attention(q, q_ts, q_hs, k, k_ts, k_hs, v, v_ts, v_hs, out, o_ts, o_hs, q_st
     return out
 
 
-def decode_attention(qkv, pos, cos, sin, k_cache, v_cache, slot, write_idx, k_len, n_q, n_kv, s_max, scale, out=None):
-    """One decode step's rope + KV-cache write + attention for B sequences (owc_decode_attention); returns [B, n_q * 128]."""
+def decode_attention(qkv, pos, cos, sin, k_cache, v_cache, slot, write_idx, k_len, n_q, n_kv, s_max, scale, out=None, *,
+                     kv_dtype="bf16", k_scale=None, v_scale=None):
+    """One decode step's rope + KV-cache write + attention for B sequences (owc_decode_attention); returns [B, n_q * 128].
+    kv_dtype="fp8": k_cache / v_cache hold e4m3fn codes (uint8), k_scale / v_scale the float32 row scales [slot, n_kv, s_max]."""
+    if kv_dtype not in ("bf16", "fp8"):
+        raise ValueError(f"kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}")
+    if kv_dtype == "fp8":
+        assert k_cache.dtype == torch.uint8 and v_cache.dtype == torch.uint8 and k_scale.dtype == F32 and v_scale.dtype == F32
     b = qkv.shape[0]
     if out is None:
         out = torch.empty((b, n_q * 128), dtype=BF16, device=qkv.device)
     _call("owc_decode_attention", _dev(qkv), qkv.data_ptr(), qkv.stride(0), pos.data_ptr(), cos.data_ptr(), sin.data_ptr(),
           k_cache.data_ptr(), v_cache.data_ptr(), slot.data_ptr(), write_idx.data_ptr(), k_len.data_ptr(), out.data_ptr(),
-          out.stride(0), b, n_q, n_kv, s_max, float(scale))
+          out.stride(0), b, n_q, n_kv, s_max, float(scale), _lib.KV_FP8 if kv_dtype == "fp8" else _lib.KV_BF16, ptr(k_scale), ptr(v_scale))
     return out
+
+
+def kv_quantize_fp8_(k_stage, v_stage, k8, v8, k_scale, v_scale, tok_slot, tok_idx, n_kv, s_max, bcast_first_slot=0, bcast_n_slots=0):
+    """Quantise the rows (tok_slot[t], kv head, tok_idx[t]) of one bf16 staging layer [slots, n_kv, s_max, 128] into one layer of an fp8
+    cache (codes k8 / v8 uint8, scales float32 [slots, n_kv, s_max]); tok_slot < 0: the shared-prefix row of slot bcast_first_slot goes
+    to every slot of the broadcast range (owc_kv_quantize_fp8)."""
+    assert k_stage.dtype == BF16 and v_stage.dtype == BF16 and k8.dtype == torch.uint8 and v8.dtype == torch.uint8
+    assert k_scale.dtype == F32 and v_scale.dtype == F32 and tok_slot.dtype == I32 and tok_idx.dtype == I32
+    _call("owc_kv_quantize_fp8", _dev(k8), k_stage.data_ptr(), v_stage.data_ptr(), k8.data_ptr(), v8.data_ptr(), k_scale.data_ptr(),
+          v_scale.data_ptr(), tok_slot.data_ptr(), tok_idx.data_ptr(), tok_slot.numel(), n_kv, s_max, bcast_first_slot, bcast_n_slots)
+    return k8, v8
 
 
 def embed_tokens(ids, img_index, table, img_embeds):
