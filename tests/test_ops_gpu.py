@@ -7,7 +7,7 @@ import torch
 
 from oracle import np_ops
 from oracle import qwen2vl_np as Q
-from tests.util import assert_bf16_close, bf16_randn, to_np
+from tests.util import CANARY, POISON, assert_bf16_close, assert_guard_intact, assert_same_bits, bf16_randn, embed, guarded, to_np
 
 pytestmark = pytest.mark.gpu
 I32 = torch.int32
@@ -34,6 +34,53 @@ def test_layernorm_rmsnorm(gpu, rows, d):
     idx = i32(np.arange(rows - 1, -1, -2), gpu)
     y = ops.rmsnorm(x, w, 1e-6, row_index=idx)
     assert_bf16_close(to_np(y), np_ops.rms_norm(to_np(x)[to_np(idx).astype(int)], to_np(w), 1e-6, bf16=True), ulps=4.5, atol=1e-3)
+
+
+ROWWISE = [(op, rows, d) for op in ("layernorm", "rmsnorm", "rmsnorm_row_index") for rows in (5, 6) for d in (8, 1536, 1544, 4096, 4104)] + \
+          [("quantize_rows_fp8", rows, d) for rows in (5, 6) for d in (8, 2048, 2056, 4096, 4104)]
+
+
+@pytest.mark.parametrize("op,rows,d", ROWWISE)
+def test_rowwise_kernels_guard_and_strides(gpu, op, rows, d):
+    """The row-wise kernels (four rows per block: 5 and 6 rows leave a ragged last block; a `d` on each side of every switch between
+    instantiations - norm_kernel at 1536 and 4096, the quantiser at 2048 and 4096) with `x` inside a NaN-padded buffer (ldx > d) and
+    `out` - and the quantiser's `scale` - inside canaries (tests/util.py `guarded`): the guard is intact and the result equals the
+    contiguous call bit for bit."""
+    from lmms_owc_amd import ops
+
+    tag = f"{op} rows={rows} d={d}"
+    x = bf16_randn((rows, d), 500 + rows + d, 2.0, gpu)
+    g = torch.Generator().manual_seed(d)
+    w = (1 + 0.1 * torch.randn(d, generator=g)).to(torch.bfloat16).to(gpu)
+    b = (0.1 * torch.randn(d, generator=g)).to(torch.bfloat16).to(gpu)
+    _, xi = embed(x, POISON[2], after=(8, 256 + 48))
+    _, wi = embed(w, POISON[2], after=(0, 256))
+    _, bi = embed(b, POISON[2], after=(0, 256 + 16))
+    if op == "quantize_rows_fp8":
+        want_q, want_s = ops.quantize_rows_fp8(x)
+        qb, qi = guarded((rows, d), torch.uint8, gpu, CANARY[1], size_ld=xi.stride(0) * 2)
+        sb, si = guarded((rows,), torch.float32, gpu, CANARY[4])
+        ops.quantize_rows_fp8(xi, qi, si)
+        torch.cuda.synchronize()
+        assert_guard_intact(qb, qi, tag + " (codes)")
+        assert_guard_intact(sb, si, tag + " (scale)")
+        assert_same_bits(qi, want_q, tag + " (codes)")
+        assert_same_bits(si[None], want_s[None], tag + " (scale)")
+        return
+    idx = i32(np.arange(rows - 1, -1, -2), gpu) if op == "rmsnorm_row_index" else None
+    n_out = rows if idx is None else idx.numel()
+    ob, oi = guarded((n_out, d), torch.bfloat16, gpu, CANARY[2], size_ld=xi.stride(0))
+    assert oi.stride(0) != xi.stride(0) and oi.stride(0) > d and xi.stride(0) > d
+    if op == "layernorm":
+        want = ops.layernorm(x, w, b, 1e-6)
+        ops.layernorm(xi, wi, bi, 1e-6, out=oi)
+    else:
+        want = ops.rmsnorm(x, w, 1e-6, row_index=idx)
+        ops.rmsnorm(xi, wi, 1e-6, row_index=idx, out=oi)
+    torch.cuda.synchronize()
+    assert_guard_intact(ob, oi, tag)
+    assert_same_bits(oi, want, tag)
+    assert not bool(torch.isnan(oi).any()), f"{tag}: NaN in the output (padding of an input was read)"
 
 
 def test_vision_rope(gpu):

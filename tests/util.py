@@ -107,3 +107,99 @@ def assert_rel_close(got, ref, frac: float, tag: str = "") -> float:
     print(f"[rel-close] {tag}: {obs:.4f} of max|ref| (bound {frac})")
     assert obs <= frac, f"{tag}: off by {obs:.4f} of max|ref| (bound {frac})"
     return obs
+
+
+# ---- guard bands and strided operands (tests/test_gemm_guard_gpu.py, tests/test_attention_guard_gpu.py, tests/test_ops_gpu.py) ----
+# Bit patterns, by element size.  CANARY goes into OUTPUT buffers: a NaN with a payload that no kernel produces (f2bf of a NaN
+# gives the quiet NaN 0x7FC0; the fp8 quantiser saturates and never emits the e4m3fn NaN 0xFF).  POISON goes into the padding
+# of INPUT buffers: a NaN (quiet NaN for bf16 / f32, 0x7F for e4m3fn codes), so a read of padding that reaches an output shows.
+_INT_VIEW = {1: torch.uint8, 2: torch.int16, 4: torch.int32}
+CANARY = {1: 0xFF, 2: 0x7FA5, 4: 0x7FA5A5A5}
+POISON = {1: 0x7F, 2: 0x7FC0, 4: 0x7FC00000}
+
+
+def _bits(t: torch.Tensor) -> torch.Tensor:
+    return t.view(_INT_VIEW[t.element_size()])
+
+
+def _signed(pattern: int, item: int) -> int:
+    """The bit pattern as a value of the integer view's dtype (uint8 for one byte, else signed)."""
+    return pattern if item == 1 or pattern < (1 << (8 * item - 1)) else pattern - (1 << (8 * item))
+
+
+def guarded(shape, dtype, device, fill, *, before=None, after=(256, 256), ld=None, size_ld=None):
+    """A 2-D backing buffer filled with the bit pattern `fill` (CANARY / POISON above, indexed by element size) and the inner
+    view of `shape` = (rows, cols) at row before[0], column before[1] of it: (backing, inner).
+
+    before: default (1, 16 bytes) = (1, 8) for bf16 - the inner view's base address is then 16-byte aligned, which is all the
+      C ABI promises, and (leading dimensions being multiples of 32 bytes here) not 32-byte aligned.
+    after:  guard rows below and guard columns to the right of the inner view: at least the largest tile of any kernel under test
+      (256 x 256), so that a whole unpredicated tile lands inside the allocation and fails an assert instead of faulting.
+    ld:     leading dimension in elements (default: before[1] + cols + after[1], rounded up to 32 bytes); always a multiple of
+      16 bytes, which satisfies every ABI rule (bf16 % 8, fp8 codes % 16 bytes, f32 % 4).
+    size_ld: the largest leading dimension of ANY operand of the case: the backing gets as many elements as if its own rows had
+      that pitch, so a kernel that uses another operand's leading dimension for this one still writes inside it.
+    A 1-D `shape` (n,) gives a 1-D inner view (bias, scales) inside a one-row backing buffer."""
+    one_d = len(shape) == 1
+    rows, cols = (1, shape[0]) if one_d else shape
+    item = torch.empty((), dtype=dtype).element_size()
+    if before is None:
+        before = (0 if one_d else 1, 16 // item)
+    if one_d:
+        after = (0, after[1])
+    unit = 32 // item
+    if ld is None:
+        ld = -(-(before[1] + cols + after[1]) // unit) * unit
+    assert ld >= before[1] + cols + after[1] and (ld * item) % 16 == 0, (ld, before, cols, after)
+    n_rows = before[0] + rows + after[0]
+    if size_ld is not None and size_ld > ld:
+        n_rows = -(-n_rows * size_ld // ld)
+    backing = torch.empty((n_rows, ld), dtype=dtype, device=device)
+    _bits(backing).fill_(_signed(fill, item))
+    inner = backing[before[0]:before[0] + rows, before[1]:before[1] + cols]
+    assert inner.data_ptr() % 16 == 0
+    return backing, (inner[0] if one_d else inner)
+
+
+def embed(t: torch.Tensor, fill, **kw):
+    """`t` (1-D or 2-D) copied into a `guarded` buffer of its own: (backing, inner view holding t's values)."""
+    backing, inner = guarded(tuple(t.shape), t.dtype, t.device, fill, **kw)
+    inner.copy_(t)
+    return backing, inner
+
+
+def assert_guard_intact(backing, inner, tag, fill=None, owned=None):
+    """Every cell of `backing` outside the inner region still holds the fill pattern, compared AS INTEGERS.  `inner` is the view
+    `guarded` returned; `owned` (optional bool tensor of inner's shape, or of backing's shape) narrows the region the kernel may
+    write to the True cells (attention: the head_dim columns of the rows of each sequence).  Reports the first offending (row, column) pairs relative to
+    the inner view (negative / beyond its shape = outside it)."""
+    item = backing.element_size()
+    fill = CANARY[item] if fill is None else fill
+    ld = backing.stride(0)
+    off = (inner.data_ptr() - backing.data_ptr()) // item
+    r0, c0 = off // ld, off % ld
+    rows, cols = (1, inner.shape[0]) if inner.dim() == 1 else inner.shape
+    bits = _bits(backing)
+    bad = bits != _signed(fill, item)
+    if owned is None:
+        bad[r0:r0 + rows, c0:c0 + cols] = False
+    elif owned.shape == backing.shape:      # a mask over the whole backing buffer (layouts that are no rectangle of it)
+        bad &= ~owned
+    else:
+        bad[r0:r0 + rows, c0:c0 + cols] &= ~owned.reshape(rows, cols)
+    n_bad = int(bad.sum())
+    if n_bad:
+        where = torch.nonzero(bad)[:8].cpu().numpy()
+        cells = [(int(r) - r0, int(c) - c0) for r, c in where]
+        vals = [hex(int(bits[int(r), int(c)]) & ((1 << (8 * item)) - 1)) for r, c in where]
+        raise AssertionError(f"{tag}: {n_bad} cells outside the owned region of the [{rows}, {cols}] view (ld {ld}) were written; first (row, col) "
+                             f"relative to the view: {cells}, bits {vals}")
+
+
+def assert_same_bits(got: torch.Tensor, want: torch.Tensor, tag: str) -> None:
+    """Two tensors of the same shape and dtype hold the same bits (NaNs included); names the first differing cells."""
+    assert got.shape == want.shape and got.dtype == want.dtype, (tag, got.shape, want.shape, got.dtype, want.dtype)
+    diff = _bits(got.contiguous()) != _bits(want.contiguous())
+    if bool(diff.any()):
+        cells = [tuple(int(x) for x in c) for c in torch.nonzero(diff)[:8].cpu().numpy()]
+        raise AssertionError(f"{tag}: {int(diff.sum())} / {diff.numel()} cells differ from the contiguous launch; first (row, col): {cells}")
