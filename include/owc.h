@@ -478,6 +478,11 @@ int owc_llm_decode_step(owc_ctx* ctx, const owc_llm_weights* w, const owc_kv_cac
  *   the fly inside the argmax.  Sampled (`sampling` != NULL): the penalised values are written back as bf16 in front of the draw.
  *   Beam search: the caller reads its candidates through owc_beam_candidates_penalized (HF penalises the log-probabilities there)
  *   and copies a bitmap row wherever it copies a hypothesis's K / V rows.
+ *   Straggler hand-over between passes: a sequence that goes on in the next pass carries its row exactly as beam search copies
+ *   one - the caller copies the row of its old slot out beside its K / V rows and, after zeroing the next pass's bitmap and before
+ *   that pass's first owc_llm_prefill, into the row of its new slot; the prefill's shared-prefix marking covers only the slots of
+ *   its launch, so the row then changes only through the decode steps of that sequence.  The bitmap must stay allocated until the
+ *   option is switched off again: every prefill and decode step in between reads and writes through `seen`.
  *   seen == NULL switches it off (the default).  Not applied in OWC_PREFILL_SCORE_ROWS mode (loglikelihood reads raw logits). */
 int owc_llm_set_repetition_penalty(owc_ctx* ctx, float penalty, uint32_t* seen, int words_per_row);
 /* the two pieces on their own (op-level tests): mark ids[t] in bitmap row slot[t] (slot NULL: row t); penalised greedy argmax of

@@ -368,6 +368,7 @@ class Qwen2VLEngine:
         # HF's repetition penalty for every generation of this engine (1.0 = off): a model plug-in sets it from the checkpoint's
         # generation_config.json (`Qwen2VL.load_model`); `generate(..., repetition_penalty=...)` overrides it per call
         self.repetition_penalty = 1.0
+        self._seen_bits: torch.Tensor | None = None   # the seen-token bitmap of the `generate` call in progress (penalty on)
 
     # -- helpers -----------------------------------------------------------------------
     def _workspace(self, nbytes: int) -> torch.Tensor:
@@ -491,6 +492,7 @@ class Qwen2VLEngine:
             return self._generate_impl(*args, **kw)
         finally:
             self._lib.owc_llm_set_repetition_penalty(self._ctx, 1.0, None, 0)
+            self._seen_bits = None   # (only now: the context pointed at the bitmap until the line above)
 
     def _generate_impl(self, prompts: list, img_embeds: torch.Tensor | None, grids_per_prompt: list, max_new_tokens: int,
                  *, eos_token_id: int = -1, pad_token_id: int = 0, stop_check_every: int = 1, compact_rows: bool = True,
@@ -504,8 +506,9 @@ class Qwen2VLEngine:
         /root/reference/src/models/_qwen2_vl.py:319-329): HF's RepetitionPenaltyLogitsProcessor - before the argmax (or the draw)
         every token id of the sequence's prompt (image placeholders included) and everything fed to it since gets
         logit < 0 ? logit * p : logit / p in fp32 (`owc_llm_set_repetition_penalty`, include/owc.h).  1.0 = off.  The penalty is a
-        function of the sequence's own history, so batch invariance holds; straggler hand-over between passes is switched off while
-        it is on (a pass then runs every sequence to its end: the seen-token bitmap lives with the pass's cache slots).
+        function of the sequence's own history, so batch invariance holds, and the history travels with the sequence: a straggler
+        hand-over between passes (`carry`) exports the seen-token bitmap rows of the unfinished sequences beside their K / V rows and
+        the next pass starts their cache slots' rows from them.
 
         prompts[b]: 1-D int array of token ids holding image_token_id placeholders;
         grids_per_prompt[b]: list of (t, h, w) for that prompt's images, in order;
@@ -535,6 +538,9 @@ class Qwen2VLEngine:
         `carry["finished"]` = [(tag, int32 tokens incl. pad)] of carried-in sequences that ended here, `carry["out"]` = the
         export (None when nothing is left), `carry["unfinished_rows"]` = the own rows inside it (their rows of the returned
         tensor are incomplete).  A sequence's tokens do not depend on which pass finishes it (batch invariance; tested).
+        Under a repetition penalty `carry["out"]` also holds `"seen"` (device int32 [n_exported, words_per_row]: the bitmap rows of
+        the exported sequences' cache slots; the pending token is not marked yet - the pass that feeds it marks it) and `"penalty"`
+        (None and 1.0 with the penalty off).  A pass takes carried-in sequences only at THEIR penalty and row width: ValueError else.
         Returns int32 [B, max_new_tokens] (pad after EOS) and, optionally, the first-step logits [B, vocab]
         (`return_logits`) or every step's logits [max_new_tokens, B, vocab] (`return_step_logits`).
         """
@@ -547,10 +553,21 @@ class Qwen2VLEngine:
         if not rep > 0:
             raise ValueError("repetition_penalty must be > 0 (1.0 = off)")
         cin = carry.get("in") if carry is not None else None
-        if rep != 1.0 and carry is not None:
-            if cin is not None and len(cin["tags"]):
-                raise ValueError("a carried-in sequence cannot join a pass that runs with a repetition penalty")
-            carry = {**carry, "below": 0, "_caller": carry}   # no hand-over: every sequence ends in this pass
+        wpr = (d.vocab + 31) // 32                   # words of a seen-token bitmap row
+        if cin is not None and len(cin["tags"]):
+            # a carried-in sequence's penalty history is its exported bitmap row: it joins a pass of the same penalty only
+            rep_in, seen_in = float(cin.get("penalty", 1.0)), cin.get("seen")
+            if rep == 1.0 and seen_in is not None:
+                raise ValueError(f"the carried-in sequences ran under repetition penalty {rep_in} (they bring their seen-token "
+                                 f"bitmap) but this pass runs at {rep}")
+            if rep != 1.0 and seen_in is None:
+                raise ValueError(f"this pass runs under repetition penalty {rep} but the carried-in sequences bring no seen-token "
+                                 f"bitmap (their penalty: {rep_in})")
+            if rep_in != rep:
+                raise ValueError(f"the carried-in sequences ran under repetition penalty {rep_in} but this pass runs at {rep}")
+            if seen_in is not None and (seen_in.dim() != 2 or seen_in.shape[0] != len(cin["tags"]) or seen_in.shape[1] != wpr):
+                raise ValueError(f"the carried-in seen-token bitmap has shape {tuple(seen_in.shape)} but this pass needs "
+                                 f"{(len(cin['tags']), wpr)} (rows of {wpr} words for a vocabulary of {d.vocab})")
         if carry is not None and (eos_token_id < 0 or return_step_logits or return_logits or self.graph_decode):
             raise ValueError("carry needs EOS handling on and no logits output")
         NC = 0 if cin is None else len(cin["tags"])
@@ -623,11 +640,13 @@ class Qwen2VLEngine:
                                  int(sampling.get("seed", 0)) & 0xFFFFFFFFFFFFFFFF, streams.data_ptr(), step_off.data_ptr())
             samp_ref = C.byref(samp)
 
-        seen = None
+        seen_bits = None
         if rep != 1.0:   # one bitmap row of the vocabulary per cache slot: which ids the sequence has seen (prompt + fed tokens)
-            wpr = (d.vocab + 31) // 32
-            seen = torch.zeros((n_slots, wpr), dtype=I32, device=self.device)
-            _lib.check(self._lib.owc_llm_set_repetition_penalty(self._ctx, rep, seen.data_ptr(), wpr), self.dev_index)
+            # (the engine holds it until `generate` has cleared the context's pointer: every decode step marks and reads through it)
+            self._seen_bits = seen_bits = torch.zeros((n_slots, wpr), dtype=I32, device=self.device)
+            if NC:   # a carried sequence's row goes on from where the previous pass left it; from here on only the decode steps
+                seen_bits[B:Bx].copy_(cin["seen"])   # of that sequence write it (the prefill's prefix broadcast covers slots < B)
+            _lib.check(self._lib.owc_llm_set_repetition_penalty(self._ctx, rep, seen_bits.data_ptr(), wpr), self.dev_index)
         # ---- prefill in chunks of whole prompts (chunk size counted in packed ROWS: with a shared prefix every
         # prompt contributes len - P rows, so more prompts fit the same GEMM M)
         p_all = self._common_prefix(prompts, 0, B)
@@ -707,8 +726,8 @@ class Qwen2VLEngine:
                         # the flags as of the step BEFORE the one just enqueued: the GPU is busy while the host looks at them
                         pending[0].synchronize()
                         # (a row is also finished when its budget is spent: a carried sequence's cap, or this pass's own)
-                        seen = pending[1]                           # rows of the batch when the flags were taken (= n: only this block compacts)
-                        alive = np.flatnonzero((flags[:seen].numpy() == 0) & (budget[row_of[:seen]] > pending[2]))
+                        n_then = pending[1]                         # rows of the batch when the flags were taken (= n: only this block compacts)
+                        alive = np.flatnonzero((flags[:n_then].numpy() == 0) & (budget[row_of[:n_then]] > pending[2]))
                         pending = None
                         if len(alive) == 0:
                             break
@@ -720,8 +739,8 @@ class Qwen2VLEngine:
                         # the next one - with passes of different generation lengths or carried-in sequences T_out exceeds what
                         # an own row's slot was sized for.  The next step (j + 1) writes at w0 + j; the flags are one step old.
                         crowded = False
-                        if compact and len(alive) < seen:
-                            gone = np.setdiff1d(row_of[:seen], row_of[alive], assume_unique=True)
+                        if compact and len(alive) < n_then:
+                            gone = np.setdiff1d(row_of[:n_then], row_of[alive], assume_unique=True)
                             ahead_ = j + 1 + max(1, stop_check_every)             # rows linger until the next look at the flags
                             crowded = bool((st_host[2, gone] + ahead_ >= s_max).any() or (st_host[1, gone] + ahead_ >= d.max_positions).any())
                         if compact and (crowded or n - len(alive) >= max(1, n // 64)):
@@ -743,9 +762,7 @@ class Qwen2VLEngine:
         if carry is not None:
             self._carry_export(carry, cin, B, NC, n if T_out > 1 else Bx, cur, state, done2, row_of, steps_run, out_tokens, kc, vc,
                                s_max, Bx, max_new_tokens, forced_tokens, pad_token_id, n_slots,
-                               None if sampling is None else sid)
-            if "_caller" in carry:   # (repetition penalty: the engine ran on a copy with the hand-over off - hand the results back)
-                carry["_caller"].update({k: v for k, v in carry.items() if k not in ("_caller", "below")})
+                               None if sampling is None else sid, seen_bits, rep)
             out_tokens = out_tokens[:B, :max_new_tokens]
         if stats is not None:
             stats["live_rows_per_step"] = live_per_step
@@ -939,10 +956,11 @@ class Qwen2VLEngine:
         return (out, scores) if return_scores else out
 
     def _carry_export(self, carry, cin, B, NC, n, cur, state, done2, row_of, steps_run, out_tokens, kc, vc, s_max, Bx,
-                      max_new_tokens, forced_tokens, pad_token_id, n_slots, stream_of=None) -> None:
+                      max_new_tokens, forced_tokens, pad_token_id, n_slots, stream_of=None, seen_bits=None, rep=1.0) -> None:
         """End of a pass with straggler hand-over: after the last enqueued step has run, split the rows that were still in the
         decode batch into finished ones and sequences that go on in the next pass (their K / V rows, pending token, position and
-        remaining budget are copied out: the pass's own cache is released with the pass)."""
+        remaining budget are copied out: the pass's own cache is released with the pass; under a repetition penalty also the
+        `seen_bits` rows of their cache slots, exactly as beam search copies a row when a hypothesis changes its slot)."""
         d = self.d
         torch.cuda.current_stream().synchronize()
         st = state[cur, :, :n].cpu().numpy()                        # [7, n] after the last step (advanced in place)
@@ -984,6 +1002,9 @@ class Qwen2VLEngine:
         sel = torch.from_numpy(idx.astype(np.int64)).to(self.device)
         kv = [t[:, :, :, :w_c].index_select(1, sel) for t in self._kv_views(kc, vc, n_slots, s_max)]   # fp8: codes, then the row scales
         k_out, v_out = kv[0], kv[1]
+        seen_out = None
+        if seen_bits is not None:   # the bitmap rows of the exported sequences' cache SLOTS, as the last enqueued step left them
+            seen_out = seen_bits.index_select(0, torch.from_numpy(st[4, comp].astype(np.int64)).to(self.device))
         tokens, tags, forced_rest = [], [], []
         for r in idx:
             r = int(r)
@@ -1001,7 +1022,7 @@ class Qwen2VLEngine:
         carry["out"] = {"k": k_out, "v": v_out, "cached": cached, "tok": st[0, comp].astype(np.int64), "pos": st[1, comp].astype(np.int64),
                         "emitted": emitted[idx], "remaining": (cap - emitted)[idx], "tokens": tokens, "tags": tags,
                         "forced_rest": forced_rest, "stream": None if stream_of is None else np.asarray(stream_of)[idx],
-                        "kv_scales": kv[2:]}
+                        "kv_scales": kv[2:], "seen": seen_out, "penalty": float(rep) if seen_bits is not None else 1.0}
 
     def score(self, ids, img_embeds: torch.Tensor | None, grids: list, start: int, *, img_rows=None):
         """Teacher-forced scoring of ONE token sequence (prompt + continuation) in a single prefill: the logits of the positions

@@ -402,7 +402,7 @@ class PassPipeline:
             return n, nxt >= len(units)
 
         t_begin = time.perf_counter()
-        self.last_timing = {"chunks": 0, "pass_sizes": []}
+        self.last_timing = {"chunks": 0, "pass_sizes": [], "handed_over": 0}   # handed_over: sequences exported to a following pass
         last_size, left = 0, len(requests)
         while left:
             top_up()
@@ -458,6 +458,7 @@ class PassPipeline:
                 for tag, full in carry["finished"]:
                     rows[tag] = cut(full)
                 carried, skip = carry["out"], set(carry["unfinished_rows"])
+                self.last_timing["handed_over"] += 0 if carried is None else len(carried["tags"])
             inflight.append((host, ev, prep.get("groups", []), launched, skip))
             launched += prep["n"]
             last_size = prep["n"]
