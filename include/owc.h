@@ -226,7 +226,9 @@ int owc_embed_tokens(owc_ctx* ctx, const int32_t* ids, const int32_t* img_index,
  *   largest (exactly HF's TopKLogitsWarper, which removes `scores < k-th value`); where the top-p cut falls inside a run of equal
  *   bf16 logits, HF keeps a prefix of the run in its unspecified sort order - this library keeps the same NUMBER of them and takes
  *   the lowest token ids.  Hence top_k = 1 with a top_p < 1 (Qwen2-VL's generation_config.json: top_k 1, top_p 0.001) leaves exactly
- *   one token, the lowest id among the maxima: the draw equals owc_argmax_bf16 bit for bit, ties included. */
+ *   one token, the lowest id among the maxima: the draw equals owc_argmax_bf16 bit for bit, ties included.  (Under a repetition
+ *   penalty owc_llm_prefill / owc_llm_decode_step answer such a request with owc_argmax_penalized_bf16's token: see
+ *   owc_llm_set_repetition_penalty.) */
 typedef struct owc_sampling {
   float temperature; /* > 0 */
   int32_t top_k;
@@ -430,7 +432,9 @@ size_t owc_llm_workspace_bytes(const owc_llm_weights* w, int T, int n_seq);
  *   every position); the last layer then runs on every row and the workspace must be sized with owc_llm_workspace_bytes(w, T, n_out).
  * Writes the KV cache and next_tok[n_out] = argmax of those rows' logits - or, with `sampling`, one draw per row at step 0
  * (row j of this launch is original batch row sampling_row0 + j for the random stream).
- * `logits_out` (optional, [n_out, vocab] bf16) receives the logits. */
+ * `logits_out` (optional, [n_out, vocab] bf16) receives the logits: the RAW lm_head rows - except for a sampled launch under a
+ * repetition penalty that draws (see owc_llm_set_repetition_penalty), where the rows hold the penalised values written back as
+ * bf16, i.e. exactly what the draw read. */
 enum { OWC_PREFILL_LAST_TOKENS = 0, OWC_PREFILL_SCORE_ROWS = 1 };
 int owc_llm_prefill(owc_ctx* ctx, const owc_llm_weights* w, const owc_kv_cache* cache,
                     const int32_t* ids, const int32_t* img_index, const void* img_embeds,
@@ -454,6 +458,7 @@ int owc_llm_prefill(owc_ctx* ctx, const owc_llm_weights* w, const owc_kv_cache* 
  *   forced_tok (optional, int32 indexed by ORIGINAL row): teacher forcing - the token fed to the next step, and the
  *     one whose EOS finishes the sequence, is forced_tok[row]; out_tokens still receives the step's own argmax.
  *   sampling (optional): the next token is a draw (owc_sampling) at step = the output column instead of the argmax.
+ *   logits_out (optional, [B, vocab] bf16): the step's logits, with the same contents as owc_llm_prefill's.
  *   step_state (optional, int32[1] on the device): when non-NULL the output column is read from step_state[0] (`step` is
  *     ignored) and, after the step, pos[b], write_idx[b], k_len[b] and step_state[0] are incremented IN PLACE, so that
  *     consecutive decode steps are byte-identical launch sequences: capture one in a hipGraph and replay it. */
@@ -475,7 +480,19 @@ int owc_llm_decode_step(owc_ctx* ctx, const owc_llm_weights* w, const owc_kv_cac
  *   ZEROED by the caller before a sequence's prefill; owc_llm_prefill marks the prompt ids (tok_slot; shared-prefix rows in every
  *   slot of the launch), owc_llm_decode_step marks the token it is fed (slot[b]) - under teacher forcing the forced token, as HF's
  *   input_ids would hold - and both apply the penalty through the bitmap row of the sequence.  Greedy: exact fp32 arithmetic on
- *   the fly inside the argmax.  Sampled (`sampling` != NULL): the penalised values are written back as bf16 in front of the draw.
+ *   the fly inside the argmax.  Sampled (`sampling` != NULL): the penalised values are written back as bf16 in front of the draw
+ *   (one rounding HF does not do; without a top-k / top-p cut it moves the distribution by at most (exp(2 e) - 1) / 2 in total
+ *   variation, e = max |penalised logit| * 2^-8 / temperature), and `logits_out` holds those written-back rows.
+ *   Sampled with top_k == 1: HF keeps the maxima of the fp32 penalised scores, and the rounding could add a token to them (a
+ *   penalised 20.0 / 1.05 = 19.0476 rounds to 19.0 and ties with an unseen 19.0).  Two cases, both exact:
+ *   - no top-p cut (top_p <= 0 or >= 1).  This is what the reference's call leaves of a Qwen2-VL generation_config.json (top_k 1,
+ *     top_p 0.001) when the task sets no top_p: it passes top_p = None explicitly, which replaces the file's value.  The write-back
+ *     gives the fp32 maxima their rounded value r and moves every OTHER token that rounds to r one bf16 step below it (below +-0:
+ *     -2^-126); the draw's kept set is then HF's - the penalised argmax where the fp32 maximum is unique, a draw among true fp32
+ *     ties.  `logits_out` holds those rows.
+ *   - 0 < top_p < 1 (the file's own values, when a task passes them): one token survives, so such a generation takes the greedy
+ *     path above - the argmax of the fp32 penalised scores, lowest id on ties, token for token what `sampling` == NULL returns;
+ *     nothing is written back, nothing is drawn, `logits_out` holds the RAW rows.
  *   Beam search: the caller reads its candidates through owc_beam_candidates_penalized (HF penalises the log-probabilities there)
  *   and copies a bitmap row wherever it copies a hypothesis's K / V rows.
  *   Straggler hand-over between passes: a sequence that goes on in the next pass carries its row exactly as beam search copies
@@ -485,11 +502,15 @@ int owc_llm_decode_step(owc_ctx* ctx, const owc_llm_weights* w, const owc_kv_cac
  *   option is switched off again: every prefill and decode step in between reads and writes through `seen`.
  *   seen == NULL switches it off (the default).  Not applied in OWC_PREFILL_SCORE_ROWS mode (loglikelihood reads raw logits). */
 int owc_llm_set_repetition_penalty(owc_ctx* ctx, float penalty, uint32_t* seen, int words_per_row);
-/* the two pieces on their own (op-level tests): mark ids[t] in bitmap row slot[t] (slot NULL: row t); penalised greedy argmax of
- * bf16 logits rows through bitmap rows row_slot[r] (NULL: row r), lowest index on ties. */
+/* the pieces on their own (op-level tests): mark ids[t] in bitmap row slot[t] (slot NULL: row t); penalised greedy argmax of
+ * bf16 logits rows through bitmap rows row_slot[r] (NULL: row r), lowest index on ties; the sampled path's write-back - every
+ * marked column v < vocab of row r becomes bf16(x < 0 ? x * penalty : x / penalty) IN PLACE (fp32 arithmetic, one round-to-nearest-
+ * even), nothing else of the row is touched (any ld >= vocab; bits at or above vocab and words past the vocabulary are ignored). */
 int owc_seen_mark(owc_ctx* ctx, const int32_t* ids, const int32_t* slot, int n, int vocab, uint32_t* seen, int words_per_row, void* stream);
 int owc_argmax_penalized_bf16(owc_ctx* ctx, const void* logits, int64_t ld, int rows, int vocab, const uint32_t* seen, int words_per_row,
                               const int32_t* row_slot, float penalty, int32_t* out, void* stream);
+int owc_penalize_rows_bf16(owc_ctx* ctx, void* logits, int64_t ld, int rows, int vocab, const uint32_t* seen, int words_per_row,
+                           const int32_t* row_slot, float penalty, void* stream);
 
 /* first-token bookkeeping after prefill: same done/pad/out_tokens update as a decode step. */
 int owc_decode_update(owc_ctx* ctx, int32_t* next_tok, uint8_t* done, int32_t* out_tokens,

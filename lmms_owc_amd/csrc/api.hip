@@ -16,7 +16,7 @@
 
 extern "C" {
 
-int owc_abi_version(void) { return 21; }
+int owc_abi_version(void) { return 22; }
 
 int owc_has_timing_knobs(void) {   // 1 only in libowc_hip_timing.so (tools/); the product library answers 0
 #ifdef OWC_TIMING_KNOBS
@@ -223,6 +223,13 @@ int owc_beam_candidates_penalized(owc_ctx* ctx, const void* logits, int64_t ld, 
   if (!(penalty > 0.f)) OWC_FAIL(ctx, OWC_ERR_ARG, "owc_beam_candidates_penalized: need penalty > 0");
   RET(ctx, "owc_beam_candidates_penalized", owc_launch_beam_candidates_penalized(logits, ld, rows, vocab, k, seen, words_per_row, row_slot,
                                                                                   penalty, logz, top_val, top_idx, ST(stream)));
+}
+
+int owc_penalize_rows_bf16(owc_ctx* ctx, void* logits, int64_t ld, int rows, int vocab, const uint32_t* seen, int words_per_row,
+                           const int32_t* row_slot, float penalty, void* stream) {
+  if (!ctx || !logits || !seen) return OWC_ERR_ARG;
+  if (ld < vocab) OWC_FAIL(ctx, OWC_ERR_SHAPE, "owc_penalize_rows_bf16: ld < vocab");
+  RET(ctx, "owc_penalize_rows_bf16", owc_launch_penalize_rows(logits, ld, rows, vocab, seen, words_per_row, row_slot, nullptr, penalty, ST(stream)));
 }
 
 int owc_sample_bf16(owc_ctx* ctx, const void* logits, int64_t ld, int rows, int vocab, const owc_sampling* sampling,

@@ -490,6 +490,47 @@ __global__ __launch_bounds__(1024) void penalize_rows_kernel(bf16_t* __restrict_
   }
 }
 
+// The write-back in front of a top_k == 1 draw.  HF keeps the maxima of the fp32 penalised scores (TopKLogitsWarper removes what is
+// below the largest value) and draws among them; after a plain bf16 write-back sample_kernel would keep every token whose ROUNDED
+// value equals the rounded maximum - also one that is smaller in fp32 (a seen 20.0 / 1.05 = 19.0476 -> 19.0 beside an unseen 19.0).
+// Rounding is monotone, so such a token can only TIE with the maximum's bf16 value r, never exceed it: this kernel writes r to the
+// true fp32 maxima (amax[row]: one of them, from argmax_penalized_kernel) and moves every other token that would hold r one bf16
+// step below it; all remaining seen columns get the ordinary write-back.  The kept set of the draw is then exactly HF's.
+__device__ __forceinline__ unsigned short bf16_step_below(unsigned short b) {
+  if ((b & 0x7fffu) == 0) return 0x8080u;                  // below +-0: the negative number of smallest normal magnitude
+  if (b & 0x8000u) return (unsigned short)(b + 1);         // negative: one step up in magnitude
+  const unsigned short nb = (unsigned short)(b - 1);
+  return (nb & 0x7f80u) ? nb : (unsigned short)0;          // positive: one step down, subnormals go to +0
+}
+
+__global__ __launch_bounds__(1024) void penalize_rows_top1_kernel(bf16_t* __restrict__ logits, long ld, int V, const unsigned* __restrict__ seen,
+                                                                  int wpr, const int* __restrict__ row_slot, const int* __restrict__ row_index,
+                                                                  float penalty, const int* __restrict__ amax) {
+  const int row = blockIdx.x;
+  bf16_t* x = logits + (long)row * ld;
+  const int ri = row_index ? row_index[row] : row;
+  const unsigned* bits = seen + (long)(row_slot ? row_slot[ri] : ri) * wpr;
+  int a = amax[row];
+  a = a < 0 ? 0 : (a >= V ? V - 1 : a);
+  float m = bf2f(x[a]);                                     // read by every thread before any thread writes the row
+  if ((bits[a >> 5] >> (a & 31)) & 1u) m = rep_penalize(m, penalty);
+  __syncthreads();
+  const bf16_t r = f2bf(m);
+  const unsigned short rb = __builtin_bit_cast(unsigned short, r);
+  const bf16_t below = __builtin_bit_cast(bf16_t, bf16_step_below(rb));
+  for (int i = threadIdx.x; i < V; i += blockDim.x) {
+    const bool hit = (bits[i >> 5] >> (i & 31)) & 1u;
+    const float p = hit ? rep_penalize(bf2f(x[i]), penalty) : bf2f(x[i]);
+    if (p == m) {
+      x[i] = r;
+    } else {
+      const bf16_t b = f2bf(p);
+      if (bf2f(b) == bf2f(r)) x[i] = below;
+      else if (hit) x[i] = b;
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------------------
 // Temperature / top-k / top-p sampling of one token per row (HF GenerationMixin._sample with TemperatureLogitsWarper ->
 // TopKLogitsWarper -> TopPLogitsWarper -> softmax -> multinomial; reached from the reference at src/models/_qwen2_vl.py:319-329
@@ -1253,6 +1294,13 @@ int owc_launch_penalize_rows(void* logits, long ld, int rows, int V, const unsig
                              const int* row_index, float penalty, hipStream_t st) {
   if (rows <= 0 || V <= 0 || !seen || wpr * 32 < V || !(penalty > 0.f)) return OWC_ERR_SHAPE;
   hipLaunchKernelGGL(penalize_rows_kernel, dim3(rows), dim3(1024), 0, st, (bf16_t*)logits, ld, V, seen, wpr, row_slot, row_index, penalty);
+  return hipGetLastError() == hipSuccess ? OWC_OK : OWC_ERR_HIP;
+}
+
+int owc_launch_penalize_rows_top1(void* logits, long ld, int rows, int V, const unsigned* seen, int wpr, const int* row_slot,
+                                  const int* row_index, float penalty, const int* amax, hipStream_t st) {
+  if (rows <= 0 || V <= 0 || !seen || !amax || wpr * 32 < V || !(penalty > 0.f)) return OWC_ERR_SHAPE;
+  hipLaunchKernelGGL(penalize_rows_top1_kernel, dim3(rows), dim3(1024), 0, st, (bf16_t*)logits, ld, V, seen, wpr, row_slot, row_index, penalty, amax);
   return hipGetLastError() == hipSuccess ? OWC_OK : OWC_ERR_HIP;
 }
 

@@ -64,6 +64,8 @@ int owc_launch_argmax_penalized(const void* logits, long ld, int rows, int V, co
                                 const int* row_index, float penalty, int* out, hipStream_t st);
 int owc_launch_penalize_rows(void* logits, long ld, int rows, int V, const unsigned* seen, int wpr, const int* row_slot,
                              const int* row_index, float penalty, hipStream_t st);
+int owc_launch_penalize_rows_top1(void* logits, long ld, int rows, int V, const unsigned* seen, int wpr, const int* row_slot,
+                                  const int* row_index, float penalty, const int* amax, hipStream_t st);
 int owc_launch_beam_candidates(const void* logits, long ld, int rows, int V, int K, float* logz, float* top_val, int* top_idx,
                                hipStream_t st);
 int owc_launch_beam_candidates_penalized(const void* logits, long ld, int rows, int V, int K, const unsigned* seen, int wpr,

@@ -282,6 +282,19 @@ static int llm_layers(owc_ctx* ctx, const owc_llm_weights* w, const owc_kv_cache
   return OWC_OK;
 }
 
+// Sampling parameters that leave ONE survivor, the maximum (top_k 1 cuts to the maximal value, a top_p < 1 to the lowest id among
+// its ties: Qwen2-VL's generation_config.json, top_k 1 / top_p 0.001).  Under a repetition penalty HF's survivor is the argmax of
+// the fp32 penalised scores; sample_kernel would see them rounded to bf16 by penalize_rows_kernel, and the rounding can tie a
+// penalised maximum with a lower unseen id (20.0 / 1.05 = 19.0476 -> 19.0).  Such a request takes the penalised argmax instead:
+// no write-back, no draw, temperature irrelevant.  A property of the generation's parameters, so every decode step of it - and a
+// captured graph of one - has the same launch sequence.
+static bool single_survivor(const owc_sampling* s) { return s && s->top_k == 1 && s->top_p > 0.f && s->top_p < 1.f; }
+// top_k 1 WITHOUT a top-p cut - what the reference's call leaves of that file when the task sets no top_p (it passes top_p = None
+// explicitly, which replaces the file's value): HF keeps every maximum of the fp32 penalised scores and draws among them.  The
+// write-back of such a generation keeps the rounded values of all other tokens below the maxima's (penalize_rows_top1_kernel), so
+// sample_kernel's kept set is HF's: the penalised argmax wherever the fp32 maximum is unique, a draw among true fp32 ties.
+static bool top1_draw(const owc_sampling* s) { return s && s->top_k == 1 && !single_survivor(s); }
+
 int owc_llm_prefill(owc_ctx* ctx, const owc_llm_weights* w, const owc_kv_cache* cache,
                     const int32_t* ids, const int32_t* img_index, const void* img_embeds,
                     const int32_t* pos3, const int32_t* tok_slot, const int32_t* tok_idx,
@@ -344,12 +357,19 @@ int owc_llm_prefill(owc_ctx* ctx, const owc_llm_weights* w, const owc_kv_cache* 
   OWC_TRY(owc_launch_rmsnorm(xl, d, w->final_norm_w, last, d, n_out, d, w->rms_eps, nullptr, st));
   OWC_TRY(owc_launch_gemm_bf16(last, d, w->lm_head_w, d, nullptr, nullptr, 0, logits, w->vocab, n_out,
                                w->vocab, d, OWC_EPI_NONE, ctx->zeros, st));
-  if (sampling && !scoring) {   // first new token by a draw at step 0; the stream ids are indexed by original batch row
+  if (sampling && !scoring && !(rep && single_survivor(sampling))) {   // first new token by a draw at step 0; the stream ids are indexed by original batch row
     if (!sampling->stream_id && sampling_row0) OWC_FAIL(ctx, OWC_ERR_ARG, "owc_llm_prefill: sampling_row0 != 0 needs explicit stream ids");
     owc_sampling sp = *sampling;
     if (sp.stream_id) sp.stream_id += sampling_row0;
     if (sp.step_offset) sp.step_offset += sampling_row0;
-    if (rep) OWC_TRY(owc_launch_penalize_rows(logits, w->vocab, n_out, w->vocab, ctx->rep_seen, ctx->rep_wpr, tok_slot, last_index, ctx->rep_penalty, st));
+    if (rep && top1_draw(sampling)) {   // next_tok carries the penalised argmax from one kernel to the next; the draw overwrites it
+      OWC_TRY(owc_launch_argmax_penalized(logits, w->vocab, n_out, w->vocab, ctx->rep_seen, ctx->rep_wpr, tok_slot, last_index, ctx->rep_penalty,
+                                          next_tok, st));
+      OWC_TRY(owc_launch_penalize_rows_top1(logits, w->vocab, n_out, w->vocab, ctx->rep_seen, ctx->rep_wpr, tok_slot, last_index,
+                                            ctx->rep_penalty, next_tok, st));
+    } else if (rep) {
+      OWC_TRY(owc_launch_penalize_rows(logits, w->vocab, n_out, w->vocab, ctx->rep_seen, ctx->rep_wpr, tok_slot, last_index, ctx->rep_penalty, st));
+    }
     OWC_TRY(owc_launch_sample(logits, w->vocab, n_out, w->vocab, &sp, nullptr, 0, nullptr, next_tok, st));
   } else if (rep) {
     OWC_TRY(owc_launch_argmax_penalized(logits, w->vocab, n_out, w->vocab, ctx->rep_seen, ctx->rep_wpr, tok_slot, last_index, ctx->rep_penalty,
@@ -406,8 +426,13 @@ int owc_llm_decode_step(owc_ctx* ctx, const owc_llm_weights* w, const owc_kv_cac
   OWC_TRY(owc_launch_rmsnorm(x, d, w->final_norm_w, last, d, B, d, w->rms_eps, nullptr, st));
   OWC_TRY(owc_launch_gemm_bf16(last, d, w->lm_head_w, d, nullptr, nullptr, 0, logits, w->vocab, B,
                                w->vocab, d, OWC_EPI_NONE, ctx->zeros, st));
-  if (sampling) {
-    if (rep) OWC_TRY(owc_launch_penalize_rows(logits, w->vocab, B, w->vocab, ctx->rep_seen, ctx->rep_wpr, slot, nullptr, ctx->rep_penalty, st));
+  if (sampling && !(rep && single_survivor(sampling))) {
+    if (rep && top1_draw(sampling)) {   // tok_io carries the penalised argmax from one kernel to the next; the draw overwrites it
+      OWC_TRY(owc_launch_argmax_penalized(logits, w->vocab, B, w->vocab, ctx->rep_seen, ctx->rep_wpr, slot, nullptr, ctx->rep_penalty, tok_io, st));
+      OWC_TRY(owc_launch_penalize_rows_top1(logits, w->vocab, B, w->vocab, ctx->rep_seen, ctx->rep_wpr, slot, nullptr, ctx->rep_penalty, tok_io, st));
+    } else if (rep) {
+      OWC_TRY(owc_launch_penalize_rows(logits, w->vocab, B, w->vocab, ctx->rep_seen, ctx->rep_wpr, slot, nullptr, ctx->rep_penalty, st));
+    }
     OWC_TRY(owc_launch_sample(logits, w->vocab, B, w->vocab, sampling, out_row, step, step_state, tok_io, st));
   } else if (rep) {
     OWC_TRY(owc_launch_argmax_penalized(logits, w->vocab, B, w->vocab, ctx->rep_seen, ctx->rep_wpr, slot, nullptr, ctx->rep_penalty, tok_io, st));

@@ -527,8 +527,12 @@ class Qwen2VLEngine:
         independently of its neighbours, so the tokens equal the uncompacted run bit for bit (tested).
         `sampling` (optional): {"temperature": T > 0, "top_k": int (0 off), "top_p": float (None / >= 1 off), "seed": int,
         "stream_ids": int per prompt (default: its index)} - HF's `do_sample` path (temperature -> top-k -> top-p -> multinomial) on
-        the library's documented Philox stream; a sequence's draws depend on (seed, its stream id, step) only.
-        `stats` (optional dict) receives the live-row count of every step.
+        the library's documented Philox stream; a sequence's draws depend on (seed, its stream id, step) only.  Under a repetition
+        penalty the draw reads the penalised logits written back as bf16 (the step logits returned are those rows); with top_k 1
+        the kept set is held to the maxima of the fp32 penalised scores, as HF's is: without a top-p cut by a write-back that
+        keeps every other token's rounded value below theirs, with 0 < top_p < 1 (one survivor) by taking the penalised greedy
+        token, the returned logits then staying raw (include/owc.h, owc_llm_set_repetition_penalty).
+        `stats` (optional dict) receives the live-row count of every step and `graph_replayed_steps` (0 on the eager path).
         `carry` (optional dict; EOS handling on): straggler hand-over between consecutive passes of a task.  In:
         `carry["in"]` - the unfinished sequences of the previous pass (`carry["out"]` of that call), which join this pass's decode
         steps as extra rows with their own KV rows, pending token and remaining budget; `carry["below"]` - once this pass's OWN
@@ -672,6 +676,7 @@ class Qwen2VLEngine:
         _lib.check(rc, self.dev_index)
         live_per_step = [Bx]
         steps_run = 0
+        graph_replays = 0                                          # decode steps replayed from the captured hipGraph (`stats`)
         row_of = np.arange(Bx)                                     # compact row -> row of out_tokens (host mirror of state[6])
         if T_out > 1:
             q_start = self._i32(ar * (d.n_q_heads + 2 * Hkv))      # functions of the compact row index: prefixes stay valid
@@ -710,6 +715,7 @@ class Qwen2VLEngine:
                 # the capture did not execute anything: replay for steps 2 .. T-1
                 for j in range(2, max_new_tokens):
                     graph.replay()
+                    graph_replays += 1
                     live_per_step.append(B)
                     if watch and j % max(stop_check_every, 8) == 0 and int(done2[0].cpu().numpy().min()) == 1:
                         break
@@ -766,6 +772,7 @@ class Qwen2VLEngine:
             out_tokens = out_tokens[:B, :max_new_tokens]
         if stats is not None:
             stats["live_rows_per_step"] = live_per_step
+            stats["graph_replayed_steps"] = graph_replays
             stats["decode_events"][1].record()
         if return_step_logits:
             return out_tokens, step_logits

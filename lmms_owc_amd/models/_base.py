@@ -684,7 +684,10 @@ def sampling_from_gen_kwargs(gen_kwargs: dict, default_top_k: int = 50) -> dict 
     Reference (src/models/_qwen2_vl.py:308-329, _llava_hf.py:355-376): `temperature` (default 0), `top_p` (default None),
     `num_beams` (default 1) from the request's gen_kwargs, `do_sample = temperature > 0`.  HF then samples through
     temperature -> top-k -> top-p with top_k from the checkpoint's generation_config.json (HF's own default is 50; Qwen2-VL's
-    ships `top_k: 1`, which makes its sampling the argmax) - `default_top_k` carries that value.  `num_beams` > 1 with temperature 0
+    ships `top_k: 1`, which makes its sampling the argmax) - `default_top_k` carries that value.  `top_p` is NOT taken from that
+    file: the reference passes `top_p=gen_kwargs["top_p"]` explicitly, None when the task sets none, and an explicit None replaces
+    the file's value in `GenerationConfig.update` (checked on transformers 5.15) - so a sampled Qwen2-VL request without a task
+    top_p runs as {temperature, top_k 1, no top-p cut}, under the file's repetition penalty.  `num_beams` > 1 with temperature 0
     is beam search (`beams_from_gen_kwargs`, `Qwen2VLEngine.generate_beam`); with temperature > 0 (beam sampling) it raises.  The
     random stream is the library's documented Philox stream keyed by torch's seed (the reference seeds torch with `--seed`, eval_model.py), one stream per DOCUMENT."""
     t = gen_kwargs.get("temperature", 0) or 0

@@ -178,8 +178,16 @@ def embed_tokens(ids, img_index, table, img_embeds):
     return out
 
 
-def argmax_bf16(logits):
-    out = torch.empty((logits.shape[0],), dtype=I32, device=logits.device)
+def _out(out, shape, dtype, device):
+    """The caller's output buffer (checked: dtype, shape, unit inner stride, same device) or a fresh one."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    assert out.dtype == dtype and tuple(out.shape) == tuple(shape) and out.device == device and out.stride(-1) == 1
+    return out
+
+
+def argmax_bf16(logits, out=None):
+    out = _out(out, (logits.shape[0],), I32, logits.device)
     _call("owc_argmax_bf16", _dev(logits), logits.data_ptr(), logits.stride(0), logits.shape[0],
           logits.shape[1], out.data_ptr())
     return out
@@ -191,46 +199,60 @@ def seen_mark_(seen, ids, slot=None):
     return seen
 
 
-def argmax_penalized_bf16(logits, seen, penalty: float, row_slot=None):
+def argmax_penalized_bf16(logits, seen, penalty: float, row_slot=None, out=None):
     """Greedy argmax of bf16 logits [rows, vocab] under HF's repetition penalty: ids marked in bitmap row row_slot[r] (None: r) of
     `seen` [slots, words >= vocab / 32] get score < 0 ? score * p : score / p in fp32 first: `owc_argmax_penalized_bf16`."""
-    out = torch.empty((logits.shape[0],), dtype=I32, device=logits.device)
+    out = _out(out, (logits.shape[0],), I32, logits.device)
     _call("owc_argmax_penalized_bf16", _dev(logits), logits.data_ptr(), logits.stride(0), logits.shape[0], logits.shape[1],
-          seen.data_ptr(), seen.shape[1], _lib.ptr(row_slot), float(penalty), out.data_ptr())
+          seen.data_ptr(), seen.stride(0), _lib.ptr(row_slot), float(penalty), out.data_ptr())
     return out
 
 
-def beam_candidates(logits, k: int):
-    """bf16 logits [rows, vocab] -> (logz float32 [rows], top_val float32 [rows, k], top_idx int32 [rows, k]): `owc_beam_candidates`."""
+def penalize_rows_bf16_(logits, seen, penalty: float, row_slot=None):
+    """IN PLACE: the sampled path's write-back of HF's repetition penalty - every column of bf16 logits [rows, vocab] (any row stride)
+    marked in bitmap row row_slot[r] (None: r) of `seen` [slots, words >= vocab / 32] becomes bf16(x < 0 ? x * p : x / p), computed
+    in fp32: `owc_penalize_rows_bf16`."""
+    assert logits.dtype == BF16 and logits.dim() == 2 and logits.stride(1) == 1 and seen.dim() == 2 and seen.stride(1) == 1
+    _call("owc_penalize_rows_bf16", _dev(logits), logits.data_ptr(), logits.stride(0), logits.shape[0], logits.shape[1],
+          seen.data_ptr(), seen.stride(0), _lib.ptr(row_slot), float(penalty))
+    return logits
+
+
+def beam_candidates(logits, k: int, out=None):
+    """bf16 logits [rows, vocab] -> (logz float32 [rows], top_val float32 [rows, k], top_idx int32 [rows, k]): `owc_beam_candidates`.
+    `out`: optional (logz, top_val, top_idx) buffers, each contiguous."""
     rows = logits.shape[0]
-    logz = torch.empty((rows,), dtype=F32, device=logits.device)
-    top_val = torch.empty((rows, k), dtype=F32, device=logits.device)
-    top_idx = torch.empty((rows, k), dtype=I32, device=logits.device)
+    o = out or (None, None, None)
+    logz = _out(o[0], (rows,), F32, logits.device)
+    top_val = _out(o[1], (rows, k), F32, logits.device)
+    top_idx = _out(o[2], (rows, k), I32, logits.device)
+    assert top_val.is_contiguous() and top_idx.is_contiguous()
     _call("owc_beam_candidates", _dev(logits), logits.data_ptr(), logits.stride(0), rows, logits.shape[1], int(k), logz.data_ptr(),
           top_val.data_ptr(), top_idx.data_ptr())
     return logz, top_val, top_idx
 
 
-def beam_candidates_penalized(logits, k: int, seen, penalty: float, row_slot=None):
+def beam_candidates_penalized(logits, k: int, seen, penalty: float, row_slot=None, out=None):
     """`beam_candidates` under HF's repetition penalty, applied to the LOG-PROBABILITIES as HF's beam search does: ids marked in bitmap
     row row_slot[r] (None: r) of `seen` [slots, words >= vocab / 32] get lp < 0 ? lp * p : lp / p.  Returns (logz float32 [rows],
-    top_val float32 [rows, k] = the k largest penalised log-probs, top_idx int32 [rows, k]): `owc_beam_candidates_penalized`."""
+    top_val float32 [rows, k] = the k largest penalised log-probs, top_idx int32 [rows, k]): `owc_beam_candidates_penalized`.
+    `out`: optional (logz, top_val, top_idx) buffers, each contiguous."""
     rows = logits.shape[0]
-    logz = torch.empty((rows,), dtype=F32, device=logits.device)
-    top_val = torch.empty((rows, k), dtype=F32, device=logits.device)
-    top_idx = torch.empty((rows, k), dtype=I32, device=logits.device)
+    o = out or (None, None, None)
+    logz = _out(o[0], (rows,), F32, logits.device)
+    top_val = _out(o[1], (rows, k), F32, logits.device)
+    top_idx = _out(o[2], (rows, k), I32, logits.device)
+    assert top_val.is_contiguous() and top_idx.is_contiguous()
     _call("owc_beam_candidates_penalized", _dev(logits), logits.data_ptr(), logits.stride(0), rows, logits.shape[1], int(k),
-          seen.data_ptr(), seen.shape[1], _lib.ptr(row_slot), float(penalty), logz.data_ptr(), top_val.data_ptr(), top_idx.data_ptr())
+          seen.data_ptr(), seen.stride(0), _lib.ptr(row_slot), float(penalty), logz.data_ptr(), top_val.data_ptr(), top_idx.data_ptr())
     return logz, top_val, top_idx
 
 
 def sample_bf16(logits, temperature: float, top_k: int = 0, top_p: float | None = None, seed: int = 0, stream_ids=None, row_map=None,
-                step: int = 0):
+                step: int = 0, out=None):
     """One draw per row of bf16 logits [rows, vocab] by owc_sampling (HF temperature -> top-k -> top-p -> multinomial; the library's
     Philox stream: key = seed, counter = (stream id of the row's ORIGINAL row, step))."""
-    import ctypes as C
-
-    out = torch.empty((logits.shape[0],), dtype=I32, device=logits.device)
+    out = _out(out, (logits.shape[0],), I32, logits.device)
     sp = _lib.Sampling(float(temperature), int(top_k or 0), float(top_p) if top_p else 0.0, int(seed) & 0xFFFFFFFFFFFFFFFF,
                        _lib.ptr(stream_ids), None)
     _call("owc_sample_bf16", _dev(logits), logits.data_ptr(), logits.stride(0), logits.shape[0], logits.shape[1], C.byref(sp),
@@ -238,9 +260,9 @@ def sample_bf16(logits, temperature: float, top_k: int = 0, top_p: float | None 
     return out
 
 
-def token_logprob_bf16(logits, target):
+def token_logprob_bf16(logits, target, out=None):
     """log softmax(logits[r])[target[r]] (fp32; 0 where target[r] < 0) for bf16 logits [rows, vocab], int32 targets [rows]."""
-    out = torch.empty((logits.shape[0],), dtype=torch.float32, device=logits.device)
+    out = _out(out, (logits.shape[0],), F32, logits.device)
     _call("owc_token_logprob_bf16", _dev(logits), logits.data_ptr(), logits.stride(0), target.data_ptr(), logits.shape[0],
           logits.shape[1], out.data_ptr())
     return out

@@ -115,3 +115,82 @@ def test_repetition_penalty_restatement_matches_hf_processor_and_generate_merges
             break
     # the penalty decided tokens (this seeded model repeats itself when left alone), and passing 1.0 explicitly switches it off
     assert flips >= 1 and plain.sequences[0].tolist() != seq
+
+
+def _hf_chain(logits, hist, penalty, T, k, p):
+    """transformers' own processors in the order `generate` applies them to a sampled request: repetition penalty -> temperature ->
+    top-k -> top-p; float64 probabilities of the processed scores."""
+    from transformers.generation.logits_process import (RepetitionPenaltyLogitsProcessor, TemperatureLogitsWarper, TopKLogitsWarper,
+                                                        TopPLogitsWarper)
+
+    ids = torch.from_numpy(np.asarray(hist, np.int64))[None]
+    scores = RepetitionPenaltyLogitsProcessor(penalty=penalty)(ids, torch.from_numpy(np.asarray(logits, np.float32))[None].clone())
+    scores = TemperatureLogitsWarper(T)(ids, scores)
+    if k:
+        scores = TopKLogitsWarper(top_k=k)(ids, scores)
+    if p is not None:
+        scores = TopPLogitsWarper(top_p=p)(ids, scores)
+    return torch.softmax(scores[0].double(), -1).numpy()
+
+
+@pytest.mark.parametrize("V", [1003, 152064])
+def test_penalty_then_warpers_is_the_order_of_the_chain(V):
+    """The composition the GPU tests hold penalise-then-sample to (tests/test_logits_consumers_gpu.py): sampling_probs(
+    repetition_penalty_scores(x)) == transformers' processors applied as penalty -> temperature -> top-k -> top-p, on the rows those
+    tests use; the penalty has to come BEFORE the cuts (cutting first keeps another set).  And `generate` itself applies that order:
+    the processed scores a sampled, penalised `generate` call of a tiny GPT-2 returns equal the composition on its raw logits."""
+    from oracle import qwen2vl_np as Q
+    from tests.penalty_cases import CONFIGS, sampling_row
+
+    row, hist, penalty = sampling_row(V)
+    for T, k, p in CONFIGS:
+        want = _hf_chain(row, hist, penalty, T, k, p)
+        got = S.sampling_probs(Q.repetition_penalty_scores(row, hist, penalty), T, k, p)
+        assert np.array_equal(got > 0, want > 0) and np.abs(got - want).max() <= 1e-6, (T, k, p)
+        if k or p:
+            cut_first = S.sampling_probs(row, T, k, p) > 0
+            assert not np.array_equal(cut_first, want > 0), "on this row the order would not show"
+    if V != 1003:
+        return
+    from transformers import GenerationConfig, GPT2Config, GPT2LMHeadModel
+
+    torch.manual_seed(3)
+    m = GPT2LMHeadModel(GPT2Config(n_layer=1, n_head=2, n_embd=16, vocab_size=50, n_positions=32, bos_token_id=0, eos_token_id=49)).eval()
+    m.generation_config = GenerationConfig(do_sample=True, temperature=0.7, top_k=6, top_p=0.8, repetition_penalty=1.3, eos_token_id=49, pad_token_id=0)
+    ids = torch.tensor([[3, 4, 5, 3]])
+    with torch.no_grad():
+        out = m.generate(ids, do_sample=True, temperature=0.7, top_p=0.8, num_beams=1, max_new_tokens=8, eos_token_id=49, pad_token_id=0,
+                         output_logits=True, output_scores=True, return_dict_in_generate=True)
+    seq = out.sequences[0].tolist()
+    moved = 0
+    for j, (raw, proc) in enumerate(zip(out.logits, out.scores)):
+        hist_j = seq[:len(ids[0]) + j]
+        want = torch.softmax(proc[0].double(), -1).numpy()
+        got = S.sampling_probs(Q.repetition_penalty_scores(raw[0].float().numpy(), hist_j, 1.3), 0.7, 6, 0.8)
+        assert np.array_equal(got > 0, want > 0) and np.abs(got - want).max() <= 1e-6, j
+        moved += int(not np.array_equal(S.sampling_probs(raw[0].float().numpy(), 0.7, 6, 0.8) > 0, want > 0))
+    assert len(out.scores) >= 4 and moved >= 1      # (the penalty moved a kept set: without it the comparison above would not see it)
+
+
+@pytest.mark.parametrize("V", [1003, 152064])
+def test_bf16_write_back_costs_at_most_the_derived_total_variation(V):
+    """The sampled path writes the penalised logits back as bf16 in front of the draw: one rounding HF does not do.  Where no cut
+    applies (top_k 0, no top_p) its cost is bounded: rounding to nearest moves a penalised logit l' by at most |l'| 2^-8 (half a
+    bf16 step), so every unnormalised weight exp(l' / T) and their sum move by a factor within exp(+-e), e = max |l'| 2^-8 / T, every
+    probability by a factor within exp(+-2e), and the total variation from HF's unrounded distribution, (1/2) sum |p - q|, is at most
+    (exp(2e) - 1) / 2.  Asserted on the rows of the GPU test, at the temperatures of its configs."""
+    from oracle import np_ops
+    from oracle import qwen2vl_np as Q
+    from tests.penalty_cases import CONFIGS, sampling_row
+
+    row, hist, penalty = sampling_row(V)
+    f32 = Q.repetition_penalty_scores(row, hist, penalty)
+    rounded = np_ops.bf16_round(f32)
+    assert not np.array_equal(rounded, f32)                                   # the rounding does something on this row
+    assert (np.abs(rounded.astype(np.float64) - f32) <= np.abs(f32).astype(np.float64) * 2.0 ** -8).all()
+    for T, _, _ in CONFIGS:
+        eps = float(np.abs(f32).max()) * 2.0 ** -8 / T
+        tv = 0.5 * np.abs(S.sampling_probs(rounded, T) - S.sampling_probs(f32, T)).sum()
+        bound = (np.exp(2 * eps) - 1) / 2
+        print(f"[write-back] V={V} T={T}: total variation {tv:.3e} (bound {bound:.3e})")
+        assert 0 < tv <= bound, (T, tv, bound)

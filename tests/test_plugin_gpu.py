@@ -338,6 +338,14 @@ def test_real_checkpoint_loading_path(gpu, tmp_path):
     stop2 = np.flatnonzero(toks2 == s["<|im_end|>"])
     direct2 = lm2.tokenizer.batch_decode([toks2[: stop2[0]] if len(stop2) else toks2], skip_special_tokens=True)[0]
     assert lm2.generate_until([task.instances[0]])[0] == direct2
+    # a SAMPLED request as the reference sends it: temperature from the task, top_k 1 from the file, top_p passed as None (which
+    # replaces the file's 0.001).  HF keeps the maxima of the fp32 penalised scores; the engine's draw is held to exactly that set,
+    # so the answer is the penalised greedy one (wherever the fp32 maximum is unique, it IS the greedy token)
+    hot = load_task("synthetic:3:56x56:2")
+    hot.generation_kwargs.update({"temperature": 0.01})
+    hot.build_all_requests(limit=None, rank=0, world_size=1)
+    lm2.task_dict[hot.task_name] = hot.dataset
+    assert lm2.generate_until([hot.instances[0]])[0] == direct2
 
 
 def test_sentence_encoder_loads_from_directory(gpu, tmp_path, monkeypatch):

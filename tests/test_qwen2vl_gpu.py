@@ -544,3 +544,216 @@ def test_repetition_penalty_against_hf_generate_golden(setup, gpu):
         if not np.array_equal(g[f"{name}_bf16_tokens"], g[f"{name}_bf16_tokens_without_penalty"]):
             assert not np.array_equal(free, toks), name      # without the penalty the engine does what HF does without it: something else
     assert decisive >= 12, decisive
+
+
+# ---- sampled decoding under the repetition penalty: the VALUES of the path (penalize_rows_kernel + sample_kernel inside
+# owc_llm_prefill / owc_llm_decode_step), and the request that leaves a single survivor --------------------------------------------
+SHIPPED = {"temperature": 0.01, "top_k": 1, "top_p": 0.001, "seed": 3}     # Qwen2-VL's generation_config.json
+DRAWN = {"temperature": 0.8, "top_k": 20, "top_p": 0.9, "seed": 7}         # a request that really draws
+PEN_T = 10
+
+
+@pytest.fixture(scope="module")
+def penalty_setups(setup, gpu):
+    """Five (engine, prompts) setups, each with F = its own penalised (1.3) greedy tokens and R = the RAW step logits [T, B, V] of an
+    un-penalised run teacher-forced on F: the image prompts of the penalty test; a shared-prefix engine on text prompts with a common
+    head; an engine whose prefill takes >= 3 launches (sampling_row0 != 0, the rows map through last_index); the fp8 KV cache; 40
+    text prompts (more (row, step) pairs for the single-survivor check)."""
+    from lmms_owc_amd.engine.qwen2vl import Qwen2VLDims, Qwen2VLEngine, Qwen2VLWeights
+
+    cfg, w, eng, g = setup
+    cases = []
+    for case in ("a", "b"):
+        grid = [tuple(r) for r in g[f"{case}_grid"].tolist()]
+        cases.append((g[f"{case}_ids"], grid, recipes.pixel_values(grid, 7)))
+    cases.append((recipes.prompt_ids(cfg, [(1, 4, 4)], seed=99), [(1, 4, 4)], recipes.pixel_values([(1, 4, 4)], 8)))
+    emb = eng.encode_images(torch.from_numpy(np.concatenate([c[2] for c in cases])).to(torch.bfloat16).to(gpu), [gg for c in cases for gg in c[1]])
+    r = np.random.default_rng(5)
+    head = r.integers(10, 400, 7)
+    text = [np.concatenate([head, r.integers(10, 400, 3 + i)]).astype(np.int64) for i in range(5)]
+    many = [r.integers(10, 400, 6 + (i % 7)).astype(np.int64) for i in range(40)]
+    shared = Qwen2VLEngine(eng.w, vit_chunk_tokens=64, prefill_chunk_tokens=4096, share_prefix=True, min_shared_prefix=2)
+    assert shared._common_prefix(text, 0, len(text)) == 7
+    chunked = Qwen2VLEngine(eng.w, vit_chunk_tokens=64, prefill_chunk_tokens=24, share_prefix=False)
+    launches = []
+    inner = chunked._prefill_chunk
+    chunked._prefill_chunk = lambda *a, **k: (launches.append((a[5], a[6])), inner(*a, **k))[1]    # (b0, b1) of every prefill launch
+    kv8 = Qwen2VLEngine(Qwen2VLWeights.from_state_dict(Qwen2VLDims(**{**eng.d.__dict__, "kv_dtype": "fp8"}), w, gpu))
+    out = []
+    for tag, e, prompts, em, grids in (("image", eng, [c[0] for c in cases], emb, [c[1] for c in cases]),
+                                       ("shared-prefix", shared, text, None, [[] for _ in text]),
+                                       ("chunked-prefill", chunked, text, None, [[] for _ in text]),
+                                       ("fp8-kv", kv8, text, None, [[] for _ in text]),
+                                       ("many", eng, many, None, [[] for _ in many])):
+        F = to_np(e.generate(prompts, em, grids, PEN_T, repetition_penalty=1.3)).astype(np.int64)
+        del launches[:]
+        _, R = e.generate(prompts, em, grids, PEN_T, forced_tokens=F, return_step_logits=True)
+        if tag == "chunked-prefill":
+            assert len(launches) >= 3 and launches[-1][0] > 0, launches
+        out.append(dict(tag=tag, eng=e, prompts=prompts, emb=em, grids=grids, F=F, R=R))
+    return out
+
+
+@pytest.fixture(scope="module")
+def forced_sets(setup, penalty_setups):
+    """`penalty_setups` plus one wider set: 600 text prompts, 24 steps, F = the UN-penalised greedy tokens (this model repeats itself
+    when left alone, so its favourite tokens are in the history and the penalty decides many steps), R = the raw logits under F."""
+    cfg, w, eng, g = setup
+    r = np.random.default_rng(2024)
+    wide = [r.integers(10, 400, 6 + (i % 9)).astype(np.int64) for i in range(600)]
+    none = [[] for _ in wide]
+    Fw = to_np(eng.generate(wide, None, none, 24)).astype(np.int64)
+    _, Rw = eng.generate(wide, None, none, 24, forced_tokens=Fw, return_step_logits=True)
+    return list(penalty_setups) + [dict(tag="wide", eng=eng, prompts=wide, emb=None, grids=none, F=Fw, R=Rw)]
+
+
+def _penalised(R, prompts, F, penalty):
+    """fp32 [T, B, V]: HF's processed scores of every (step, row) - the raw logits R[j, b] penalised over prompt b + F[b, :j]."""
+    R = to_np(R)
+    return np.stack([np.stack([Q.repetition_penalty_scores(R[j, b], np.concatenate([prompts[b], F[b, :j]]), penalty)
+                               for b in range(R.shape[1])]) for j in range(R.shape[0])])
+
+
+def test_sampled_path_values_under_the_repetition_penalty(penalty_setups, gpu):
+    """What a sampled request under a repetition penalty COMPUTES, through prefill and decode.  Teacher-forced on fixed tokens F:
+    run 1 (no penalty) gives the raw logits R, run 2 (sampling + penalty 1.3) gives P - `logits_out` receives the rows the draw
+    read - and the drawn tokens.  Asserted for every step j and row b, as bits: P[j, b] == bf16_round(repetition_penalty_scores(
+    R[j, b], prompt_b + F[b, :j], 1.3)) - the right bitmap row at prefill (row_slot[row_index[row]]: several launches, a shared
+    prefix) and at decode (row_slot[row]), the right direction, every word of the row; P != R on every row; every drawn token lies
+    in the oracle's kept set of P[j, b]; under the shipped top_k 1 / top_p 0.001 the token is the argmax of the fp32 penalised scores
+    (test_single_survivor_sampling_equals_penalised_greedy states why)."""
+    from oracle import np_ops
+    from oracle import sampling_np as S
+    from tests.util import assert_same_bits
+
+    p = 1.3
+    for s in penalty_setups:
+        e, prompts, F = s["eng"], s["prompts"], s["F"]
+        B, V = len(prompts), s["R"].shape[2]
+        toks, P = e.generate(prompts, s["emb"], s["grids"], PEN_T, forced_tokens=F, return_step_logits=True, sampling=DRAWN, repetition_penalty=p)
+        toks = to_np(toks).astype(np.int64)
+        f32 = _penalised(s["R"], prompts, F, p)
+        want = torch.from_numpy(np_ops.bf16_round(f32)).to(torch.bfloat16).to(gpu)
+        assert_same_bits(P.reshape(PEN_T * B, V), want.reshape(PEN_T * B, V), f"{s['tag']}: written-back rows (row = step * {B} + batch row)")
+        assert bool((P != s["R"]).any(dim=2).all()), f"{s['tag']}: a row came back un-penalised"
+        Pn = to_np(P)
+        for j in range(PEN_T):
+            for b in range(B):
+                assert S.sampling_probs(Pn[j, b], DRAWN["temperature"], DRAWN["top_k"], DRAWN["top_p"])[toks[b, j]] > 0, (s["tag"], j, b, toks[b, j])
+        one = to_np(e.generate(prompts, s["emb"], s["grids"], PEN_T, forced_tokens=F, sampling=SHIPPED, repetition_penalty=p)).astype(np.int64)
+        assert np.array_equal(one, np.argmax(f32, 2).T), s["tag"]
+
+
+def test_single_survivor_sampling_equals_penalised_greedy(setup, penalty_setups, gpu):
+    """top_k == 1 with 0 < top_p < 1 leaves one token: HF's is the argmax of the fp32 processed scores.  The sampler would read the
+    penalised values rounded to bf16 (a seen 20.0 / 1.05 = 19.0476 -> 19.0 ties with an unseen 19.0 of a lower id), so owc_llm_prefill
+    and owc_llm_decode_step answer such a request under a penalty with `owc_argmax_penalized_bf16`'s token (fp32, lowest id).
+    Free-running: the engine under {temperature 0.01, top_k 1, top_p 0.001} + penalty == the penalised greedy tokens - batched image
+    prompts, shared prefix, 40 prompts, the graph-replayed decode, row compaction with an EOS."""
+    from lmms_owc_amd.engine.qwen2vl import Qwen2VLEngine
+
+    cfg, w, eng, g = setup
+    by = {s["tag"]: s for s in penalty_setups}
+    graph = Qwen2VLEngine(eng.w, vit_chunk_tokens=64, prefill_chunk_tokens=4096, share_prefix=False, graph_decode=True)
+    for p in (1.05, 1.3):
+        for tag, e in (("image", eng), ("shared-prefix", by["shared-prefix"]["eng"]), ("many", eng), ("shared-prefix", graph)):
+            s = by[tag]
+            kw = dict(repetition_penalty=p)
+            greedy = to_np(e.generate(s["prompts"], s["emb"], s["grids"], PEN_T, **kw))
+            st = {}
+            assert np.array_equal(to_np(e.generate(s["prompts"], s["emb"], s["grids"], PEN_T, sampling=SHIPPED, stats=st, **kw)), greedy), (p, tag)
+            assert st["graph_replayed_steps"] == (PEN_T - 2 if e is graph else 0), (tag, st["graph_replayed_steps"])   # the graph leg replays
+        s = by["many"]
+        greedy = to_np(eng.generate(s["prompts"], None, s["grids"], PEN_T, repetition_penalty=p))
+        vals, counts = np.unique(greedy[:, 1:6], return_counts=True)
+        kw = dict(eos_token_id=int(vals[np.argmax(counts)]), pad_token_id=0, repetition_penalty=p)
+        st = {}
+        c0 = to_np(eng.generate(s["prompts"], None, s["grids"], PEN_T, compact_rows=False, **kw))
+        c1 = to_np(eng.generate(s["prompts"], None, s["grids"], PEN_T, compact_rows=True, sampling=SHIPPED, stats=st, **kw))
+        assert np.array_equal(c0, c1) and min(st["live_rows_per_step"]) < len(s["prompts"]), p
+
+
+def test_single_survivor_sampling_forced_on_pairs_where_the_write_back_would_differ(forced_sets, gpu):
+    """The single-survivor rule where it decides a token.  Teacher-forced on F, from the raw logits R of `forced_sets` (the five
+    setups and the wide set): the host computes a = argmax of the fp32 penalised
+    scores and b = lowest-index argmax of their bf16 rounding (what the sampler would keep after the write-back); under {temperature
+    0.01, top_k 1, top_p 0.001} the engine's token must be a at EVERY (row, step), for penalties 1.05 / 1.1 / 1.3 / 1.5, and
+    `logits_out` holds the raw rows (nothing is written back on this path).  This proves something only where a != b: at least 3
+    such pairs are required.  Found on MI355X: 83 of 59 920 pairs (82 in the wide set - 36 / 27 / 17 / 2
+    at the four penalties - and 1 in the 40-prompt setup; none in the four small ones).  Before the single-survivor branch existed
+    the engine returned b on those pairs (this test fails there)."""
+    from oracle import np_ops
+
+    differ, pairs, raw_kept = 0, 0, True
+    for s in forced_sets:
+        T = s["F"].shape[1]
+        for p in (1.05, 1.1, 1.3, 1.5):
+            f32 = _penalised(s["R"], s["prompts"], s["F"], p)
+            a, b = np.argmax(f32, 2).T, np.argmax(np_ops.bf16_round(f32), 2).T           # [B, T]; np.argmax: lowest index among maxima
+            toks, lg = s["eng"].generate(s["prompts"], s["emb"], s["grids"], T, forced_tokens=s["F"], return_step_logits=True,
+                                         sampling=SHIPPED, repetition_penalty=p)
+            toks = to_np(toks).astype(np.int64)
+            print(f"[single-survivor] {s['tag']} p={p}: {int((a != b).sum())} of {a.size} pairs with a != b; engine == a on "
+                  f"{int((toks == a).sum())}, == b on {int((toks == b).sum())}")
+            assert np.array_equal(toks, a), (s["tag"], p, np.argwhere(toks != a)[:8].tolist())
+            raw_kept = raw_kept and torch.equal(lg.view(torch.int16), s["R"].view(torch.int16))
+            differ += int((a != b).sum())
+            pairs += a.size
+    print(f"[single-survivor] {differ} of {pairs} (row, step) pairs where the bf16 write-back would have changed the token")
+    assert differ >= 3, differ
+    assert raw_kept, "logits_out of a single-survivor generation must hold the raw rows"
+
+
+TOP1 = {"temperature": 0.01, "top_k": 1, "seed": 3}     # what the reference's call leaves of the shipped file: top_p passed as None
+
+
+def _bf16_step_below(r):
+    """float32 array of bf16 values -> the next bf16 value below each, as the library defines it: one bf16 step towards -inf; below
+    +-0 the negative number of smallest normal magnitude, and positive subnormals are skipped (the step below 2^-126 is +0)."""
+    b = (np.ascontiguousarray(r, np.float32).view(np.uint32) >> 16).astype(np.int64)
+    down = np.where((b - 1) & 0x7F80, b - 1, 0)
+    nb = np.where((b & 0x7FFF) == 0, 0x8080, np.where(b & 0x8000, b + 1, down))
+    return (nb.astype(np.uint32) << 16).view(np.float32)
+
+
+def test_top_k_1_draw_under_a_penalty_keeps_exactly_the_fp32_maxima(forced_sets, gpu):
+    """The sampled request the reference really sends to a Qwen2-VL checkpoint: temperature > 0, top_k 1 from generation_config.json,
+    NO top_p (the call passes top_p=None, which replaces the file's 0.001).  HF keeps the maxima of the fp32 penalised scores and
+    draws among them.  A plain bf16 write-back would also keep a token that merely ROUNDS to the maximum's bf16 value; the top-1
+    write-back (penalize_rows_top1_kernel) moves those one bf16 step down.  Teacher-forced on F, from the raw logits R, penalties
+    1.05 / 1.1 / 1.3 / 1.5, two seeds and temperatures, every (row, step): the engine's token is one of the fp32 maxima, and THE
+    penalised argmax wherever that maximum is unique; `logits_out` holds, as bits, bf16_round(penalised) with the maxima at their
+    rounded value r and every other token that rounds to r one step below.  At least 3 pairs where the plain write-back's kept set
+    differs from HF's are required.  Found on MI355X: 159 of 59 920 pairs (157 in the wide set, 2 in the
+    40-prompt setup); 1427 pairs have tied fp32 maxima, where the token is drawn."""
+    from oracle import np_ops
+    from tests.util import assert_same_bits
+
+    differ, pairs, ties = 0, 0, 0
+    for s in forced_sets:
+        T, B = s["F"].shape[1], len(s["prompts"])
+        for p in (1.05, 1.1, 1.3, 1.5):
+            f32 = _penalised(s["R"], s["prompts"], s["F"], p)                      # [T, B, V]
+            m = f32.max(2, keepdims=True)
+            A = f32 == m                                                            # HF's kept set
+            wb = np_ops.bf16_round(f32)
+            r = np_ops.bf16_round(m)
+            old_kept = wb == r                                                      # what a plain write-back would leave to the draw
+            assert (old_kept | ~A).all()
+            want = np.where(A, r, np.where(old_kept, _bf16_step_below(r), wb)).astype(np.float32)
+            unique = A.sum(2) == 1
+            a = np.argmax(f32, 2)
+            for smp in (TOP1, {**TOP1, "temperature": 1.0, "seed": 11}):
+                toks, P = s["eng"].generate(s["prompts"], s["emb"], s["grids"], T, forced_tokens=s["F"], return_step_logits=True,
+                                            sampling=smp, repetition_penalty=p)
+                toks = to_np(toks).astype(np.int64).T                               # [T, B]
+                assert np.take_along_axis(A, toks[:, :, None], 2).all(), (s["tag"], p, "a token outside the fp32 maxima was drawn")
+                assert np.array_equal(toks[unique], a[unique]), (s["tag"], p)
+                assert_same_bits(P.reshape(T * B, -1), torch.from_numpy(want).to(torch.bfloat16).to(gpu).reshape(T * B, -1),
+                                 f"{s['tag']} p={p}: top-1 write-back (row = step * {B} + batch row)")
+            n = int((old_kept != A).any(2).sum())
+            print(f"[top1-draw] {s['tag']} p={p}: {n} of {a.size} pairs where the plain write-back keeps a token HF cannot draw; "
+                  f"{int((~unique).sum())} pairs with tied fp32 maxima")
+            differ, pairs, ties = differ + n, pairs + a.size, ties + int((~unique).sum())
+    print(f"[top1-draw] {differ} of {pairs} pairs differ; {ties} pairs with tied fp32 maxima")
+    assert differ >= 3, differ
